@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
 """bench.py -- the Gravo MG V-cycle hot path on MI355X: V-cycle wall time + solve-to-1e-4 iterations on a
-~3 M-vertex mesh Poisson problem (BASELINE.json metric), with the fine-level kernel's HBM roofline and the
-1-core CPU restatement timed beside it.
+~3 M-vertex mesh Poisson problem (BASELINE.json metric); with --full also the fine-level kernel's HBM roofline and
+the 1-core CPU restatement timed beside it.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n1 1732 --n2 1732]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n1 1732 --n2 1732] [--dump-outputs DIR] [--full]
 
 A "step" is ONE V-cycle followed by the residual check, exactly one trip of the reference's solve loop
 (gravomg/src/multigrid_solver.cpp:1411-1417), on device-resident data.  Workload:
 jittered torus 1732 x 1732 = 2 999 824 vertices, cotangent Laplacian, lhs = 1e-6*M + S, rhs = M*y,
 y ~ N(0,1) seed 42, d = 1, x0 = rhs, ratio 8, lower_bound 1000, 2+2 smoothing sweeps, M-norm stop at 1e-4.
+
+A plain run (one GPU) sets up, solves to 1e-4 once, warms up, times K steps and prints the headline line.  --full adds
+everything else the line used to carry: the cold set-up, the second solve, the kernel and level rooflines, the variants
+(other orderings, sizes, precisions and configs) and the 1-core CPU baseline.  --dump-outputs DIR writes what the timed
+steps computed: DIR/x.npy, the iterate after the last step (n x d, float64; a seeded sample of rows, listed in
+DIR/x_rows.npy, when it exceeds the size cap), and DIR/residues.npy, the residue of every timed step.
 
 For N > 1 the driver launches this file under torch.distributed.run; the finest level is row-partitioned and after
 every colour sweep each rank stores the halo entries its peers read straight into their mailboxes (device-initiated
@@ -28,10 +34,28 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured achievable)
+DUMP_CAP_BYTES = 56 << 20  # --dump-outputs: x beyond this is written as a seeded sample of rows (all files stay under 64 MB)
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+def dump_outputs(path, x, residues):
+    """What the timed steps hand a caller: the iterate after the last step (gmg_fetch_solution, n x d) and the residues of the steps."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    rows_file = os.path.join(path, "x_rows.npy")
+    if x.nbytes > DUMP_CAP_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(x.shape[0], DUMP_CAP_BYTES // (8 * max(x.shape[1], 1)) - 1, replace=False))
+        np.save(rows_file, rows.astype(np.float64))
+        x = x[rows]
+    elif os.path.exists(rows_file):
+        os.remove(rows_file)
+    np.save(os.path.join(path, "x.npy"), x)
+    np.save(os.path.join(path, "residues.npy"), np.asarray(residues, dtype=np.float64))
+    log(f"[bench] outputs: x {x.shape} + residues ({len(residues)}) -> {path}")
 
 
 def build_workload(n1, n2, order="natural"):
@@ -240,16 +264,16 @@ def main():
     ap.add_argument("--order", default="natural", choices=["natural", "random", "chunks"])
     ap.add_argument("--config", default=None, choices=["1", "2", "3", "4", "4r", "4s", "5", "5b", "6"],
                     help="profiling aid: another BASELINE config (meshgen.baseline_config) as the main workload instead of the torus --n1 x --n2")
-    ap.add_argument("--cpu-cycles", type=int, default=25, help="V-cycles timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-cycles", type=int, default=25, help="--full: V-cycles timed on the CPU oracle (0 = skip)")
     ap.add_argument("--coarse", default="auto", choices=["auto", "host", "device"],
                     help="gmg_config::coarse_mode: auto (the library default: dense inverse applied on the device while n_L <= 8192), host (LDL^T "
                          "back-substitution, one round trip per cycle), device")
     ap.add_argument("--graph", action="store_true", help="replay the cycle legs from hipGraphs (same cycle time, ~5 ms instantiation per system)")
-    ap.add_argument("--kernel-reps", type=int, default=50)
+    ap.add_argument("--kernel-reps", type=int, default=50, help="--full: launches per kernel in the roofline timings")
     ap.add_argument("--block-rows", type=int, default=None, help="block-hybrid GS rows per block (engine default if unset)")
     ap.add_argument("--block-from-level", type=int, default=None)
     ap.add_argument("--block-lanes", type=int, default=None)
-    ap.add_argument("--no-variants", action="store_true", help="skip the informational device-coarse-apply timing")
+    ap.add_argument("--no-variants", action="store_true", help="--full: skip the informational variants")
     ap.add_argument("--force-dist", action="store_true", help="use the multi-GPU code path even with one rank")
     ap.add_argument("--exchange", default="p2p", choices=["p2p", "halo", "allgather"],
                     help="N > 1: p2p = engine-driven cycle, device-initiated stores into the peers' mailboxes (falls back to halo if it "
@@ -260,10 +284,17 @@ def main():
                          "hierarchy and set_system (replicated set-up), so the set-up time and memory grow with N")
     ap.add_argument("--shard-levels", type=int, default=2, choices=[1, 2],
                     help="N > 1, p2p: levels partitioned over the ranks (2 = level 0 by rows per colour + level 1 by blocks; 1 = level 0 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: also the cold set-up, the second solve, the kernel and level rooflines, the variants and the CPU baseline "
+                         "(a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: write the iterate after the last timed step (x.npy) and the timed steps' residues (residues.npy) to DIR")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world > 1 or args.gpus > 1 or args.force_dist:
+        if args.dump_outputs:
+            ap.error("--dump-outputs is for the single-GPU line")
         from gravo_mg_amd import dist_bench
         return dist_bench.main(args)
 
@@ -292,10 +323,11 @@ def main():
     eng = cabi.Engine(coarse_mode=coarse_mode, use_graph=args.graph, **kw)
     # A cold set-up first, on a handle that was NOT told the system's sparsity pattern (prepare_structure = 0): what a system with an
     # unannounced pattern pays (a Bilaplacian's two-ring, a caller's own prolongations) -- reported as set_system_cold_ms, never as the headline
-    cold = cabi.Engine(prepare_structure=False, **kw)
-    cold.use_hierarchy(H); cold.set_mass(mass)
-    t = time.perf_counter(); cold.set_system(lhs); setup_cold_ms = 1e3 * (time.perf_counter() - t)
-    cold.close(); del cold
+    if args.full:
+        cold = cabi.Engine(prepare_structure=False, **kw)
+        cold.use_hierarchy(H); cold.set_mass(mass)
+        t = time.perf_counter(); cold.set_system(lhs); setup_cold_ms = 1e3 * (time.perf_counter() - t)
+        cold.close(); del cold
     # The default: gmg_use_hierarchy hands the engine the hierarchy's point graph -- the sparsity pattern of tau M + S -- and the structure of the
     # system (orderings, colourings, layouts, symbolic Galerkin products, symbolic LDL^T) is prepared when the hierarchy is finalized
     # (structure_prepare_ms, part of the construction like the hierarchy itself); gmg_set_system then does what depends on the VALUES: upload,
@@ -326,8 +358,9 @@ def main():
     timing = {k: eng.timing(k) for k in keys}
     # the same solve once more on the live system (what a second right-hand side costs; also shows how much of the first call was
     # one-off: page-locking, first touch of the staging buffers, a busy host right after the set-up)
-    eng.solve(rhs, tol=1e-4, stop_type=2, max_iter=100)
-    timing_again = {k: eng.timing(k) for k in ("cycles", "solve_call", "coarse_host_ms", "solve_load", "solve_fetch")}
+    if args.full:
+        eng.solve(rhs, tol=1e-4, stop_type=2, max_iter=100)
+        timing_again = {k: eng.timing(k) for k in ("cycles", "solve_call", "coarse_host_ms", "solve_load", "solve_fetch")}
 
     # ---- timed region: K V-cycles (+ residual check each) on resident data ------------------------------
     eng.load_problem(rhs, rhs)                       # x0 = rhs (gravomg_bindings/src/cpp/core.cpp:69)
@@ -338,6 +371,33 @@ def main():
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     ms_per_step = 1e3 * (t1 - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng.fetch_solution(), residues)
+
+    coarse_on_device = bool(eng.timing("coarse_on_device"))
+    coarse_inverse_ms = eng.timing("coarse_inverse_ms") if coarse_on_device else None
+    out = {
+        "metric": "V-cycle wall time (ms per V-cycle incl. residual check) + solve-to-1e-4 iterations, 3M-vertex Poisson",
+        "value": ms_per_step, "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": False, "scaling": "strong", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic",
+        "config": {"workload": workload, "n_vertices": n0, "levels": [l["n"] for l in levels], "colors": [l["n_colors"] for l in levels],
+                   "smoother": f"2+2 sweeps; level 0: multicolour Gauss-Seidel over-relaxed by {eng_omega:g} (SOR, one launch per colour); levels >= 1: "
+                               "block-hybrid Gauss-Seidel (64-row blocks: Gauss-Seidel inside a block, Jacobi between blocks, one launch per sweep)",
+                   "coarse_solve": args.coarse + (" (dense inverse applied on the device, built on the device at set_system)" if coarse_on_device else " (host LDL^T per cycle)"),
+                   "hipgraph": args.graph,
+                   "tolerance": 1e-4, "stopping_criteria": 2},
+        "iterations_to_1e-4": iters, "residue": res, "residues_to_1e-4": [float(v) for v in conv[:, 1]],
+        "solve_ms": solve_ms, "solver_timing_ms": timing,
+        "set_system_ms": setup_ms, "set_system_structure_prepared": setup_prepared, "structure_prepare_ms": structure_ms, "use_hierarchy_ms": use_hierarchy_ms,
+        "coarse_inverse_ms": coarse_inverse_ms,
+        "construct_plus_first_solve_ms": use_hierarchy_ms + setup_ms + solve_ms,
+        "mvertex_cycles_per_s": n0 / ms_per_step / 1e3,
+        "timed_residues_tail": [float(r) for r in residues[-3:]],
+    }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
 
     # ---- roofline of the dominant kernel: fine-level Gauss-Seidel colour launches (gs_color<1,1>) --------
     sweep_ms, launches = eng.bench_kernel(0, 0, d0, args.kernel_reps)
@@ -470,33 +530,18 @@ def main():
 
     cpu = cpu_baseline(H, mass, lhs, rhs, args.cpu_cycles) if args.cpu_cycles > 0 else None
 
-    out = {
-        "metric": "V-cycle wall time (ms per V-cycle incl. residual check) + solve-to-1e-4 iterations, 3M-vertex Poisson",
-        "value": ms_per_step, "unit": "ms", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": False, "scaling": "strong", "vs_baseline": None,
-        "dtype": "f64", "data": "synthetic",
-        "config": {"workload": workload, "n_vertices": n0, "levels": [l["n"] for l in levels], "colors": [l["n_colors"] for l in levels],
-                   "smoother": f"2+2 sweeps; level 0: multicolour Gauss-Seidel over-relaxed by {eng_omega:g} (SOR, one launch per colour); levels >= 1: "
-                               "block-hybrid Gauss-Seidel (64-row blocks: Gauss-Seidel inside a block, Jacobi between blocks, one launch per sweep)",
-                   "coarse_solve": args.coarse + (" (dense inverse applied on the device, built on the device at set_system)" if coarse_on_device else " (host LDL^T per cycle)"),
-                   "hipgraph": args.graph,
-                   "tolerance": 1e-4, "stopping_criteria": 2},
-        "iterations_to_1e-4": iters, "residue": res, "residues_to_1e-4": [float(v) for v in conv[:, 1]],
+    out.update({
         "iterations_reference_algorithm": cpu["iterations_to_1e-4"] if cpu else None,
-        "solve_ms": solve_ms, "solver_timing_ms": timing, "second_solve_timing_ms": timing_again,
-        "set_system_ms": setup_ms, "set_system_structure_prepared": setup_prepared, "structure_prepare_ms": structure_ms, "use_hierarchy_ms": use_hierarchy_ms,
+        "second_solve_timing_ms": timing_again,
         "set_system_cold_ms": setup_cold_ms, "coarse_inverse_ms": coarse_inverse_ms,
-        "construct_plus_first_solve_ms": use_hierarchy_ms + setup_ms + solve_ms,
         "set_system_note": "set_system_ms: the first gmg_set_system on a handle whose hierarchy announced the system's sparsity pattern (its point graph): "
                            "values up, numeric Galerkin chain, layout refill, numeric LDL^T; the structural half was done once in gmg_use_hierarchy "
                            "(structure_prepare_ms, inside use_hierarchy_ms).  set_system_cold_ms: the same call on a handle that was told nothing",
         "set_system_same_pattern_ms": repeat_ms, "set_system_same_pattern_values_only": repeat_values_only,
-        "mvertex_cycles_per_s": n0 / ms_per_step / 1e3,
-        "timed_residues_tail": [float(r) for r in residues[-3:]],
         "variants": variants,
         "roofline": roofline,
         "cpu_baseline": cpu,
-    }
+    })
     if cpu:
         out["speedup_vs_cpu_per_cycle"] = cpu["value"] / ms_per_step
     print(json.dumps(out), flush=True)

@@ -1,6 +1,6 @@
 # bench line of the current build; argument: tag
 R=$GRAFT_REPO_ROOT; T=${1:-e}; O=$R/gpurun_out/r06$T; mkdir -p $O; cd $R
-timeout -s KILL 1200 python bench.py > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+timeout -s KILL 1200 python bench.py --full > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
 python - "$O/bench.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

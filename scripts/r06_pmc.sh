@@ -3,7 +3,7 @@ TAG=$1; NAME=$2; shift; shift
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/r06$TAG; mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 pmc() { N=$1; C=$2; shift; shift
-  timeout -s KILL 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$N -- python $R/bench.py --steps 4 --warmup 1 --cpu-cycles 0 --no-variants --kernel-reps 4 "$@" > /dev/null 2> $O/pmc_$N.log
+  timeout -s KILL 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $O/pmc_$N -- python $R/bench.py --full --steps 4 --warmup 1 --cpu-cycles 0 --no-variants --kernel-reps 4 "$@" > /dev/null 2> $O/pmc_$N.log
   python $R/scripts/pmc_summary.py $(find $O/pmc_$N -name "*counter_collection.csv" | head -1) > $O/pmc_$N.txt 2>&1; rm -rf $O/pmc_$N; }
 pmc fetch_$NAME FETCH_SIZE "$@"; pmc write_$NAME WRITE_SIZE "$@"
 cat $O/pmc_fetch_$NAME.txt $O/pmc_write_$NAME.txt > $O/pmc_fetch_write_$NAME.txt; rm -f $O/pmc_fetch_$NAME.txt $O/pmc_write_$NAME.txt

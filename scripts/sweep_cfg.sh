@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: scripts/sweep_cfg.sh "<bench args 1>" "<bench args 2>" ...   -> one summary line per configuration
 for a in "$@"; do
-  python bench.py --steps 20 --warmup 3 --cpu-cycles 0 $a 2>/dev/null | python -c "
+  python bench.py --full --steps 20 --warmup 3 --cpu-cycles 0 $a 2>/dev/null | python -c "
 import json,sys
 j=json.loads(sys.stdin.read())
 k=j['roofline']['other_fine_kernels']
