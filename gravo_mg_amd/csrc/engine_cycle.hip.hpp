@@ -1017,7 +1017,7 @@ int vcycle_resident(gmg_handle h, int d, int norm_type) {
 }
 
 int check_level(gmg_handle h, int k, bool allow_coarsest) {
-    if (!h->system_ready) return fail(h, GMG_ERR_STATE, "no system set (call gmg_set_system first)");
+    if (h->live != LiveSystem::system) return fail(h, GMG_ERR_STATE, "no system set (call gmg_set_system first)");
     if (k < 0 || k > h->L || (!allow_coarsest && k == h->L)) return fail(h, GMG_ERR_INVALID, "level index out of range");
     return GMG_OK;
 }

@@ -183,6 +183,10 @@ struct DistPlan {
     std::vector<std::vector<int>> halo1, halo0r;          // [s * world + t]: x1 entries / r0 entries rank s publishes to rank t
 };
 
+// What the handle's levels hold: nothing, the structure of the prepared pattern on placeholder values (gmg_finalize_hierarchy:
+// engine_system.hip.hpp::prepare_structure), or a system to solve with
+enum class LiveSystem { none, placeholder, system };
+
 struct gmg_solver_s {
     DevPool pool;
     DistP2P* p2p = nullptr;              // engine-driven multi-GPU cycle (engine_dist.hip.hpp)
@@ -205,10 +209,9 @@ struct gmg_solver_s {
     std::vector<int> bfs_order;           // ... and the breadth-first order over the point graph, when the caller / the hierarchy object supplied one (gmg_set_fine_order)
     // The pattern the next systems are expected to have (gmg_set_fine_graph / gmg_use_hierarchy).  gmg_finalize_hierarchy then builds everything
     // STRUCTURAL for it -- orderings, colourings, layouts, symbolic Galerkin products, symbolic LDL^T: a whole set-up on placeholder values --
-    // and leaves the handle in the "placeholder" state: no system to solve with (system_ready stays false), but the first gmg_set_system whose
+    // and leaves the handle in the "placeholder" state (LiveSystem): no system to solve with, but the first gmg_set_system whose
     // pattern digest equals the prepared one only moves values (refresh_system_values), like any later system with the live pattern.
     std::shared_ptr<const FineGraph> fine_graph;
-    bool placeholder_ready = false;
     bool mass_dirty = false;              // h->mass changed while no ordering existed to permute it with: uploaded by the next set-up / refresh
     int *d_bfs_order = nullptr, *d_bfs_inv = nullptr;
     int base_order_choice = 0;            // what the last reordered set-up used: 0 cluster order, 1 breadth-first order
@@ -218,7 +221,7 @@ struct gmg_solver_s {
     std::vector<double> mass;
     std::vector<Level> lv;
     SupernodalLDLT coarse;
-    bool system_ready = false;
+    LiveSystem live = LiveSystem::none;
     int dcap = 0;
     double *d_mass = nullptr, *d_minv = nullptr;
     double* d_stage = nullptr; size_t stage_cap = 0;
@@ -259,9 +262,8 @@ struct gmg_solver_s {
     double coarse_warm_sink = 0.0;
     int coarse_pending_d = 0;
     bool poll = true;             // GMG_POLL=0: copy + hipStreamSynchronize instead (the waiting thread then sleeps instead of spinning)
-    double* d_ainv = nullptr;                              // coarse_device: dense A_L^-1, level numbering (engine.hip::build_coarse_inverse_device)
+    double* d_ainv = nullptr;                              // coarse_device: dense A_L^-1, level numbering (engine_system.hip.hpp::build_coarse_inverse_device)
     int ainv_n = 0, ainv_ld = 0;                           // ... n x n with rows ainv_ld doubles apart (n rounded up to 8: rows at 64-byte boundaries)
-    bool preparing_structure = false;                      // inside prepare_structure (placeholder values)
     bool first_sweep_fused = false;                        // enqueue_down: the restriction into the next level ran that level's first pre-sweep (launch_restrict_sweep0)
     bool coarse_device = false;                            // the coarsest solve of the live system runs on the device (gmg_config::coarse_mode, decided per system)
     std::vector<double> coarse_work;
@@ -584,15 +586,16 @@ void unbind_level0(gmg_handle h) {
     h->bound = false; h->own_x0 = h->own_b0 = h->own_r0 = nullptr;
 }
 
+void lose_live_system(gmg_handle h) { h->live = LiveSystem::none; }
+
 void drop_system(gmg_handle h) {
     h->refill_ready = false;
-    h->placeholder_ready = false;
+    lose_live_system(h);
     drop_graphs(h);
     unbind_level0(h);
     h->dist_ready = false;
     for (auto& l : h->lv) free_level(l);
     h->lv.clear();
-    h->system_ready = false;
     h->dcap = 0;
     h->loaded_d = 0;
     if (h->d_mass) { (void)dev_free(h->d_mass); h->d_mass = nullptr; }
