@@ -408,6 +408,7 @@ int gmg_debug_sell_copy(gmg_handle h, int k, int which, int64_t* slice_ptr, int*
 int gmg_get_timing(gmg_handle h, const char* key, double* out) try {
     if (!h || !key || !out) return GMG_ERR_INVALID;
     if (std::string(key) == "device_bytes_now") { *out = (double)h->pool.live_bytes; return GMG_OK; }      // device memory the handle holds at this moment (pool blocks in use)
+    if (std::string(key) == "restrict_sweeps_fused") { *out = (double)h->fused_restrictions; return GMG_OK; }      // fused restriction + first pre-sweep launches enqueued so far (gmg_config::fuse_restrict_sweep)
     auto it = h->timing.find(key);
     if (it == h->timing.end()) return fail(h, GMG_ERR_INVALID, std::string("unknown timing key: ") + key);
     *out = it->second;
@@ -1363,7 +1364,7 @@ int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const doubl
         if (pre.n_colors == -2) return GMG_ERR_INVALID;
         if (info) info[5] = pre.n_colors >= 0 ? 1 : 0;
         LevelOrdering o = make_ordering(PatternView{n, colptr, rowidx}, true, (block_rows > 0 && block_rows % 64 == 0) ? block_rows : 64, sigma, 0, nullptr, true, &pre);
-        if (o.n_colors > 256) return GMG_ERR_UNSUPPORTED;
+        if (o.n_colors > kMaxColors) return GMG_ERR_UNSUPPORTED;
         if (info) { info[0] = o.n_pad; info[1] = o.n_colors; info[2] = 0; info[3] = 0; info[4] = 0; }
         if (new2old) std::memcpy(new2old, o.new2old.data(), sizeof(int) * o.n_pad);
         if (color_begin) std::memcpy(color_begin, o.color_begin.data(), sizeof(int) * (o.n_colors + 1));
@@ -1374,7 +1375,7 @@ int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const doubl
     // (mode 2: colour-major with the locality reordering forced -- the colouring then walks a visit ORDER; mode 3: colour-major, row indices declared ascending)
     LevelOrdering o = mode == 1 ? make_block_ordering(A, block_rows)
                                 : make_ordering(A, true, (block_rows > 0 && block_rows % 64 == 0) ? block_rows : 64, sigma, mode == 2 ? 1 : 0, nullptr, mode == 3);
-    if (o.n_colors > 256) return GMG_ERR_UNSUPPORTED;
+    if (o.n_colors > kMaxColors) return GMG_ERR_UNSUPPORTED;
     SellHost sa; std::vector<double> dg; std::string e;
     if (!build_operator_sell(A, o, 0, sa, dg, e)) return GMG_ERR_NUMERIC;
     if (info) { info[0] = o.n_pad; info[1] = o.n_colors; info[2] = o.n_blocks(); info[3] = sa.stored(); info[4] = sa.nnz_real; info[5] = 0; }

@@ -687,7 +687,7 @@ void restrict_into(gmg_handle h, int k, int d, bool il) {
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
     const int fused = (k + 1 < h->L && smooth_from_zero_ok(h, c, h->cfg.pre_iters)) ? restrict_sweep0_kind<T>(h, l, c, d, il) : 0;
-    if (fused) launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused);
+    if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); }
     else launch_restrict<T>(h, l, c, d, Prec<T>::r(l), Prec<T>::b(c), il);
 }
 

@@ -817,7 +817,7 @@ private:
         // Level 0 always keeps one lane per row: the residual-norm kernels read its operator in that layout.
         const int lanes_auto = lk.n < kQuadLevelRows ? 4 : 1;
         const int lpr = (lk.ord.blocked && k > 0) ? (h->cfg.block_lanes ? h->cfg.block_lanes : lanes_auto) : 1;
-        if (lk.ord.n_colors > 255) { st.ok = false; st.err = "more than 255 colours"; return; }
+        if (lk.ord.n_colors > kMaxColors) { st.ok = false; st.err = "more than " + std::to_string(kMaxColors) + " colours"; return; }
         if (!build_operator_sell(lk.A, lk.ord, lpr, st.sa, st.dg, st.err)) { st.ok = false; return; }
         if (lk.ord.blocked && wants_block_ep(h, lpr)) {
             build_operator_blockcsr(lk.A, lk.ord, st.bc, 3);       // "explicit" part
@@ -860,7 +860,7 @@ private:
         if (!ordering_arrived(k)) return;
         h->timing["setup_wait_ordering"] += ms_since(tw);
         mark("ordering_ready_l" + std::to_string(k));
-        if (h->lv[k].ord.n_colors > 255) { rc_all = GMG_ERR_UNSUPPORTED; err_all = "more than 255 colours on level " + std::to_string(k); return; }
+        if (h->lv[k].ord.n_colors > kMaxColors) { rc_all = GMG_ERR_UNSUPPORTED; err_all = "more than " + std::to_string(kMaxColors) + " colours on level " + std::to_string(k); return; }
         rc_all = upload(h, &h->lv[k].d_new2old, h->lv[k].ord.new2old);
     }
     void wait_lhs() { if (lhs_copied.valid()) lhs_copied.wait(); }

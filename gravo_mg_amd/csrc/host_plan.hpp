@@ -74,6 +74,12 @@ struct RawVec {
     const T& operator[](size_t i) const { return p[i]; }
 };
 
+// Most colours a level may have; gmg_set_system and the planner entry gmg_host_plan_level both refuse a level with more (GMG_ERR_UNSUPPORTED).
+// What binds is the byte a row's colour is kept in on the device side (LevelOrdering::row_color of a blocked level, the partition plan's
+// colour-class table): it could name 256 colours.  255 is the stricter of the two limits the set-up (255) and the planner (256) used to apply,
+// kept so that what gmg_set_system accepts does not change and the byte value 255 is never a real colour.
+constexpr int kMaxColors = 255;
+
 struct LevelOrdering {
     int n = 0;                        // real unknowns
     int n_pad = 0;                    // device vector length (multiple of 64)

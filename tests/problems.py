@@ -5,6 +5,7 @@ from __future__ import annotations
 import functools
 
 import numpy as np
+import scipy.sparse as sp
 
 from gravo_mg_amd import cabi, meshgen
 
@@ -54,6 +55,96 @@ def sphere_problem(n=6000, lower_bound=80, order="spatial"):
     H = cabi.Hierarchy(V, neigh, lower_bound=lower_bound)
     lhs, rhs = meshgen.poisson_system(S, mass)
     return Problem(V, S, mass, H.U, lhs, rhs, f"sphere{n}-{order}")
+
+
+def _laplacian_of(W):
+    """Graph Laplacian S = diag(W 1) - W of a symmetric non-negative weight matrix (CSC, sorted)."""
+    W = sp.csc_matrix(W)
+    S = (sp.diags(np.asarray(W.sum(axis=1)).ravel()) - W).tocsc()
+    S.sort_indices()
+    return S
+
+
+def _weights(rows, cols, n, rng):
+    """Symmetric weight matrix with seeded weights in [0.5, 1.5) on the undirected edges (rows[i], cols[i])."""
+    w = 0.5 + rng.random(len(rows))
+    W = sp.coo_matrix((w, (rows, cols)), shape=(n, n)).tocsc()
+    return W + W.T
+
+
+def _grid_edges(n1, n2, offset=0):
+    idx = np.arange(n1 * n2).reshape(n1, n2) + offset
+    return (np.concatenate([idx[:-1, :].ravel(), idx[:, :-1].ravel()]), np.concatenate([idx[1:, :].ravel(), idx[:, 1:].ravel()]))
+
+
+def aggregation(n_f, n_c):
+    """Piecewise-constant prolongation: fine i -> coarse floor(i n_c / n_f), consecutive fine indices in exactly n_c non-empty groups."""
+    assert 1 <= n_c <= n_f
+    return sp.csc_matrix((np.ones(n_f), (np.arange(n_f), np.arange(n_f) * n_c // n_f)), shape=(n_f, n_c))
+
+
+def smoothed_aggregation(n_f, n_c):
+    """Rows of up to 3 entries: 1/2 on the fine row's own group, 1/4 on each neighbouring group (renormalised at the ends).  Every coarse
+    column keeps the fine rows of its own group."""
+    j = np.arange(n_f) * n_c // n_f
+    rows, cols, vals = [np.arange(n_f)], [j], [np.full(n_f, 0.5)]
+    for s in (-1, 1):
+        ok = (j + s >= 0) & (j + s < n_c)
+        rows.append(np.arange(n_f)[ok]); cols.append(j[ok] + s); vals.append(np.full(ok.sum(), 0.25))
+    U = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(n_f, n_c))
+    U = sp.diags(1.0 / np.asarray(U.sum(axis=1)).ravel()) @ U
+    return sp.csc_matrix(U)
+
+
+def synthetic_problem(graph, sizes, kind="poisson", prolong=("pc",), d=8, seed=5):
+    """A problem of exact level sizes: an operator from a made-up graph and hand-made prolongations instead of the hierarchy builder.
+
+    graph: ("chain", n) | ("grid", n1, n2) | ("diagonal", n) | ("isolated", n1, n2) -- a grid with every 20th vertex cut loose (only its
+    diagonal) | ("clique", n1, n2, m) -- a grid behind m vertices that form a clique, vertex i < m tied to grid vertex m + i | ("hub", n1, n2) --
+    a grid whose last vertex is tied to the first vertex of every level-1 group (a dense row on level 1).
+    sizes: [n_0, n_1, ..., n_L]; prolong: "pc" (aggregation) or "smooth" (3-entry rows) per level, the last one repeated.
+    kind: "poisson" lhs = S + 1e-2 M, "smoothing" lhs = M + S; M a positive lumped mass.  rhs = M y with d seeded columns."""
+    rng = np.random.default_rng(seed)
+    name = graph[0]
+    if name in ("chain", "diagonal"):
+        n = graph[1]
+        e = (np.arange(n - 1), np.arange(1, n)) if name == "chain" else (np.zeros(0, int), np.zeros(0, int))
+    elif name in ("grid", "isolated", "hub"):
+        n1, n2 = graph[1], graph[2]
+        n = n1 * n2 + (name == "hub")
+        e = _grid_edges(n1, n2)
+        if name == "isolated":
+            cut = np.arange(7, n, 20)
+            keep = ~(np.isin(e[0], cut) | np.isin(e[1], cut))
+            e = (e[0][keep], e[1][keep])
+        if name == "hub":
+            first = np.searchsorted(np.arange(n) * sizes[1] // n, np.arange(sizes[1]))
+            first = first[first != n - 1]
+            e = (np.concatenate([e[0], first]), np.concatenate([e[1], np.full(len(first), n - 1)]))
+    elif name == "clique":
+        n1, n2, m = graph[1], graph[2], graph[3]
+        n = m + n1 * n2
+        g = _grid_edges(n1, n2, offset=m)
+        a, b = np.triu_indices(m, 1)
+        e = (np.concatenate([g[0], a, np.arange(m)]), np.concatenate([g[1], b, m + np.arange(m)]))
+    else:
+        raise ValueError(graph)
+    assert sizes[0] == n, (sizes, n)
+    S = _laplacian_of(_weights(e[0], e[1], n, rng)) if len(e[0]) else sp.csc_matrix((n, n))
+    mass = 0.5 + rng.random(n)
+    if kind == "poisson":
+        lhs = (S + 1e-2 * sp.diags(mass)).tocsc()
+    elif kind == "smoothing":
+        lhs = (sp.diags(mass) + S).tocsc()
+    else:
+        raise ValueError(kind)
+    lhs.sort_indices()
+    rhs = mass[:, None] * rng.standard_normal((n, d))
+    U = []
+    for k in range(len(sizes) - 1):
+        how = prolong[min(k, len(prolong) - 1)]
+        U.append(aggregation(sizes[k], sizes[k + 1]) if how == "pc" else smoothed_aggregation(sizes[k], sizes[k + 1]))
+    return Problem(None, S, mass, U, lhs, rhs, f"{'-'.join(map(str, graph))}-{kind}-{'x'.join(map(str, sizes))}")
 
 
 def permuted_system(A, new2old):

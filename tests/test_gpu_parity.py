@@ -15,12 +15,9 @@ import pytest
 import scipy.sparse as sp
 
 from tests import problems
+from tests.parity_checks import check_block_sweeps as _check_block_sweeps, check_multicolor_gs, rel, timing_or_none
 
 pytestmark = pytest.mark.gpu
-
-
-def rel(a, b):
-    return np.linalg.norm(np.asarray(a) - np.asarray(b)) / max(np.linalg.norm(np.asarray(b)), 1e-300)
 
 
 @pytest.fixture(scope="module", params=["poisson-d1", "smoothing-d3", "pointcloud", "random-order", "irregular-sphere"])
@@ -134,66 +131,9 @@ def test_residual_from_the_sweeps_explicit_part_equals_b_minus_Ax(setup, cabi, o
     assert used > 0 or len(P.U) == 1
 
 
-def _check_block_sweeps(P, eng, oracle):
-    import scipy.sparse.linalg as spla
-    rng = np.random.default_rng(7)
-    checked = 0
-    for k in range(len(P.U)):
-        blocks = eng.level_blocks(k)
-        if blocks is None:
-            assert k == 0
-            continue
-        checked += 1
-        blk_begin, row_color = blocks
-        A = eng.level_operator(k)
-        new2old, _ = eng.level_ordering(k)
-        assert np.all(np.diff(blk_begin) % 64 == 0) and np.all(np.diff(blk_begin) <= 1024) and blk_begin[-1] == len(new2old)
-        real = new2old >= 0
-        blk_of_dev = np.repeat(np.arange(len(blk_begin) - 1), np.diff(blk_begin))
-        order = new2old[real]; blk = blk_of_dev[real]; col = row_color[real]
-        Ap = A.tocsr()[order][:, order].tocoo()
-        same = blk[Ap.row] == blk[Ap.col]
-        off = Ap.row != Ap.col
-        # proper colouring inside every block, rows colour-sorted inside a block
-        assert np.all(col[Ap.row[same & off]] != col[Ap.col[same & off]])
-        assert np.all((np.diff(col) >= 0) | (np.diff(blk) != 0))
-        keep = same & (Ap.col <= Ap.row)
-        T = sp.csr_matrix((Ap.data[keep], (Ap.row[keep], Ap.col[keep])), shape=Ap.shape)
-        for d in (1, 3):
-            b = rng.standard_normal((A.shape[0], d)); x = rng.standard_normal((A.shape[0], d))
-            want = x.copy()
-            for iters in (1, 2, 3):
-                r = oracle.residual(A, b, want)
-                step = np.empty_like(want)
-                step[order] = spla.spsolve_triangular(T, r[order], lower=True)
-                want = want + step
-                got = eng.smooth(k, b, x, iters)
-                assert rel(got, want) <= 1e-12
-    assert checked == len(P.U) - (eng.level_blocks(0) is None)       # (level 0 too where the engine blocked it: block_from_level = 0, or gmg_config::block_fine on a kNN operator)
-
-
 def test_multicolor_gs_is_reference_gs_on_permuted_system(setup_exact, oracle):
     P, eng = setup_exact
-    rng = np.random.default_rng(2)
-    for k in range(len(P.U)):
-        A = eng.level_operator(k)
-        new2old, color_begin = eng.level_ordering(k)
-        Ap, order = problems.permuted_system(A, new2old)
-        # colouring is proper: no edge inside a colour class
-        colour_of = np.empty(A.shape[0], int)
-        for c in range(len(color_begin) - 1):
-            rows = new2old[color_begin[c]:color_begin[c + 1]]
-            colour_of[rows[rows >= 0]] = c
-        coo = sp.coo_matrix(A)
-        off = coo.row != coo.col
-        assert np.all(colour_of[coo.row[off]] != colour_of[coo.col[off]])
-        for d in (1, 3):
-            b = rng.standard_normal((A.shape[0], d)); x = rng.standard_normal((A.shape[0], d))
-            for iters in (1, 2):
-                got = eng.smooth(k, b, x, iters)
-                want_p = oracle.gauss_seidel(Ap, b[order], x[order], iters)
-                want = np.empty_like(want_p); want[order] = want_p
-                assert rel(got, want) <= 1e-12
+    check_multicolor_gs(P, eng, oracle)
 
 
 def test_level0_sor_sweep_matches_model(setup, oracle):
@@ -591,7 +531,7 @@ def test_head_of_the_next_cycle_is_enqueued_ahead_of_the_decision_and_changes_no
         if spec:
             assert eng.timing("heads_enqueued") >= res["to the tolerance"][1] + 2 and eng.timing("head_decision_differs") == 0.0
         else:
-            assert not _has_timing(eng, "heads_enqueued")
+            assert timing_or_none(eng, "heads_enqueued") is None
         eng.load_problem(P.rhs, P.rhs)
         res["run_cycles"] = (eng.run_cycles(4, 2).copy(), eng.fetch_solution().copy())
         if spec:
@@ -614,10 +554,3 @@ def test_head_of_the_next_cycle_is_enqueued_ahead_of_the_decision_and_changes_no
     # the stopped iteration's x is the one after its last cycle: one cycle from x0 = rhs, whatever was in the stream behind the check
     assert np.array_equal(a["first cycle is enough"][0], a["one cycle allowed"][0])
 
-
-def _has_timing(eng, key):
-    try:
-        eng.timing(key)
-        return True
-    except Exception:
-        return False

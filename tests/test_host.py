@@ -239,6 +239,78 @@ def test_smallest_last_in_block_colouring_needs_no_more_colours_and_does_not_dep
     assert np.mean(sl["64"]["colours"]) <= 0.95 * np.mean(bfs["64"]["colours"])   # (Galerkin level of a mesh: ~13 % fewer)
 
 
+def _boundary_operators():
+    """Level-0 and level-1 operators of the synthetic boundary-shape catalogue (tests/test_gpu_boundary_shapes.py A-C)."""
+    specs = [("chain%d" % n, dict(graph=("chain", n), sizes=[n, max(1, n // 2)], prolong=("smooth",))) for n in (1, 2, 5, 63, 64, 65, 127, 128, 129, 193)]
+    specs += [("diagonal%d" % n, dict(graph=("diagonal", n), sizes=[n, max(1, n // 4)])) for n in (1, 100, 4097)]
+    specs += [("isolated", dict(graph=("isolated", 40, 40), sizes=[1600, 400])), ("hub", dict(graph=("hub", 48, 40), sizes=[1921, 480]))]
+    specs += [("clique%d" % m, dict(graph=("clique", 24, 24, m), sizes=[m + 576, (m + 576) // 4])) for m in (65, 254, 255)]
+    for name, spec in specs:
+        P = problems.synthetic_problem(**spec)
+        yield name + "-l0", sp.csc_matrix(P.lhs)
+        yield name + "-l1", sp.csc_matrix(P.U[0].T @ P.lhs @ P.U[0])
+
+
+@pytest.mark.parametrize("mode", [0, 1, 4])
+def test_layout_planner_at_boundary_shapes(cabi, mode):
+    """gmg_host_plan_level on levels smaller than a slice, at slice boundaries, without off-diagonals, with isolated rows, a dense row and
+    cliques: new2old is a permutation of the rows plus -1 padding, colour classes (mode 0, 4) and blocks (mode 1) are 64-aligned, the
+    colouring is proper, and a level of n rows and one colour is padded to the next multiple of 64."""
+    for name, A in _boundary_operators():
+        n = A.shape[0]
+        plan = cabi.host_plan_level(A, mode=mode, block_rows=256) if mode != 4 else cabi.host_plan_ahead(n, A.indptr, A.indices)
+        new2old = plan["new2old"]
+        assert len(new2old) == plan["n_pad"] and plan["n_pad"] % 64 == 0, name
+        real = new2old[new2old >= 0]
+        assert np.array_equal(np.sort(real), np.arange(n)) and np.all(new2old[new2old < 0] == -1), name
+        colour = np.empty(n, int)
+        if mode == 1:
+            bb, rc = plan["blk_begin"], plan["row_color"]
+            assert bb[0] == 0 and bb[-1] == plan["n_pad"] and np.all(np.diff(bb) % 64 == 0) and np.all(np.diff(bb) > 0), name
+            blk_dev = np.repeat(np.arange(plan["n_blocks"]), np.diff(bb))
+            blk = np.empty(n, int)
+            blk[new2old[new2old >= 0]] = blk_dev[new2old >= 0]
+            colour[new2old[new2old >= 0]] = rc[new2old >= 0]
+            coo = sp.coo_matrix(A); off = (coo.row != coo.col) & (blk[coo.row] == blk[coo.col])
+        else:
+            cb = plan["color_begin"]
+            assert len(cb) == plan["n_colors"] + 1 and cb[0] == 0 and cb[-1] == plan["n_pad"] and np.all(cb % 64 == 0) and np.all(np.diff(cb) > 0), name
+            for c in range(plan["n_colors"]):
+                rows = new2old[cb[c]:cb[c + 1]]
+                colour[rows[rows >= 0]] = c
+            coo = sp.coo_matrix(A); off = coo.row != coo.col
+        assert np.all(colour[coo.row[off]] != colour[coo.col[off]]), name             # proper
+        if (A != 0).nnz == n and mode != 1:                                          # no off-diagonals: one colour, one padded class
+            assert plan["n_colors"] == 1 and plan["n_pad"] == (n + 63) // 64 * 64, name
+            if mode != 4:
+                assert plan["sell_stored"] == 0 and plan["offdiag_nnz"] == 0, name
+    # n_pad of the smallest levels: one colour class (n = 1), or one 64-row class per colour
+    for n, want in ((1, 64), (2, 128), (63, 128), (64, 128), (65, 128)):
+        A = sp.csc_matrix(problems.synthetic_problem(("chain", n), [n, 1]).lhs)
+        plan = cabi.host_plan_level(A, mode=0) if mode != 4 else cabi.host_plan_ahead(n, A.indptr, A.indices)
+        assert plan["n_pad"] == want, (n, plan["n_pad"])
+        if mode == 1:
+            assert cabi.host_plan_level(A, mode=1)["n_pad"] == (n + 63) // 64 * 64
+
+
+@pytest.mark.parametrize("m", [254, 255, 256])
+def test_planner_and_set_up_accept_the_same_largest_colour_count(cabi, m):
+    """K_m needs m colours.  The planner entry (gmg_host_plan_level, every mode) accepts exactly what gmg_set_system accepts: at most 255
+    colours on a level (host_plan.hpp kMaxColors; set-up checked on the GPU in test_gpu_boundary_shapes.py)."""
+    K = sp.csc_matrix(np.ones((m, m)) + m * np.eye(m))
+    if m <= 255:
+        for mode in (0, 3):
+            assert cabi.host_plan_level(K, mode=mode)["n_colors"] == m
+        assert cabi.host_plan_level(K, mode=1, block_rows=256)["n_colors"] == m
+        assert cabi.host_plan_ahead(m, K.indptr, K.indices)["n_colors"] == m
+    else:
+        for call in (lambda: cabi.host_plan_level(K, mode=0), lambda: cabi.host_plan_level(K, mode=3), lambda: cabi.host_plan_level(K, mode=1, block_rows=256),
+                     lambda: cabi.host_plan_ahead(m, K.indptr, K.indices)):
+            with pytest.raises(cabi.GmgError) as ei:
+                call()
+            assert ei.value.code == cabi.GMG_ERR_UNSUPPORTED
+
+
 def test_missing_diagonal_is_a_numeric_error(cabi):
     A = sp.csc_matrix(np.array([[2.0, 1.0, 0.0], [1.0, 0.0, 1.0], [0.0, 1.0, 2.0]]))
     A.eliminate_zeros()
