@@ -744,10 +744,14 @@ void enqueue_up(gmg_handle h, int d, int k0 = 0) {
     }
 }
 
+// (n = 0 -- the block-CSR of a level that is one block has no entry -- is no launch: a grid of 0 workgroups is refused, and the error it leaves
+// behind would be reported by the next gmg_set_system on this thread)
 inline void launch_cvt(gmg_handle h, const double* src, float* dst, size_t n) {
+    if (n == 0) return;
     hipLaunchKernelGGL(gmgk::cvt_f64_to_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, src, dst, (int64_t)n);
 }
 inline void launch_cvt(gmg_handle h, const float* src, double* dst, size_t n) {
+    if (n == 0) return;
     hipLaunchKernelGGL(gmgk::cvt_f32_to_f64, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, src, dst, (int64_t)n);
 }
 

@@ -1,5 +1,6 @@
 """Checks shared by the GPU parity tests (tests/test_gpu_parity.py on the hierarchy builder's meshes, tests/test_gpu_boundary_shapes.py on
-synthetic problems of exact shapes): a device smoother against its matrix form built from the oracle's arithmetic."""
+synthetic problems of exact shapes, tests/test_gpu_sweep_counts.py at other sweep counts): a device smoother against its matrix form built
+from the oracle's arithmetic, the oracle on the device's colour ordering, which launch paths the timing keys say ran."""
 import numpy as np
 import scipy.sparse as sp
 
@@ -40,7 +41,7 @@ def check_block_sweeps(P, eng, oracle, ds=(1, 3)):
         for d in ds:
             b = rng.standard_normal((A.shape[0], d)); x = rng.standard_normal((A.shape[0], d))
             want = x.copy()
-            for iters in (1, 2, 3):
+            for iters in (1, 2, 3, 4, 5):          # (both parities of the ping-pong between x and tmp, with and without a copy back)
                 r = oracle.residual(A, b, want)
                 step = np.empty_like(want)
                 step[order] = spla.spsolve_triangular(T, r[order], lower=True)
@@ -86,3 +87,37 @@ def timing_or_none(eng, key):
         if e.code == cabi.GMG_ERR_INVALID and "unknown timing key" in str(e):
             return None
         raise
+
+
+def colour_permuted_hierarchy(P, eng, oracle, **kw):
+    """The oracle on the device's colour ordering of every level (an engine with block_rows = 0): (oracle.Hierarchy of P A P^T with the permuted
+    prolongations, the level-0 order).  kw goes to oracle.Hierarchy (pre_iters, post_iters)."""
+    L = len(P.U)
+    orders = []
+    for k in range(L):
+        n2o, _ = eng.level_ordering(k)
+        orders.append(n2o[n2o >= 0])
+    orders.append(np.arange(P.U[-1].shape[1]))
+    Up = [sp.csc_matrix(sp.csc_matrix(P.U[k]).tocsr()[orders[k]][:, orders[k + 1]]) for k in range(L)]
+    lhs_p = sp.csc_matrix(sp.csc_matrix(P.lhs).tocsr()[orders[0]][:, orders[0]])
+    O = oracle.Hierarchy(Up, P.mass[orders[0]], **kw)
+    O.set_system(lhs_p)
+    return O, orders[0]
+
+
+SWITCHES = ("speculate_head", "fuse_restrict_sweep", "uniform_slices", "fine_col16")
+
+
+def engaged(eng, switch):
+    """How much of the switched path ran, from the timing keys: heads enqueued ahead of the solve loop's decision, restrictions fused with
+    the next level's first pre-sweep, level-0 operators with 16-bit column codes, the code width of those read as uniform slices."""
+    def key(k):
+        return timing_or_none(eng, k) or 0.0      # (keys that only appear once their path has been set up or run)
+    if switch == "speculate_head":
+        return key("heads_enqueued")
+    if switch == "fuse_restrict_sweep":
+        return key("restrict_sweeps_fused")
+    ops = ("col16_l0", "col16_R_l0", "col16_P_l0")
+    if switch == "fine_col16":
+        return sum(key(k) for k in ops)
+    return sum(key(k + "_uniform_width") for k in ops)

@@ -166,6 +166,31 @@ def test_reference_call_pattern_smoothing_and_poisson(gravomg, oracle, tmp_path)
     assert np.linalg.norm(lhs @ xd - rhs) <= 1e-10 * np.linalg.norm(rhs)
 
 
+@pytest.mark.gpu
+def test_sweep_counts_reach_the_engine(gravomg, cabi):
+    """pre_iters / post_iters of the constructor (gravomg_bindings/src/gravomg/core.py:10) arrive in the engine the class owns
+    (MultigridSolver::ensureEngine): solve() with 1 + 3 gives the bits and the number of cycles of a C-ABI engine created with 1 + 3 and driven
+    with the solver's own prolongations, tolerance and stopping criterion -- and not those of a second solver left at 2 + 2.  (The class has no
+    way to change the counts after construction, so the rebuild of the engine on changed counts is not reachable from Python.)"""
+    V, F, S, M, mass = _problem()
+    neigh = gravomg.neighbors_from_stiffness(S)
+    lhs = (M + 0.001 * S).tocsr()
+    rhs = M @ V
+    solver = gravomg.MultigridSolver(V, neigh, M, lower_bound=40, tolerance=1e-4, stopping_criteria=2, max_iter=100, pre_iters=1, post_iters=3)
+    x = solver.solve(lhs, rhs)
+    eng = cabi.Engine(pre_iters=1, post_iters=3, coarse_mode=cabi.COARSE_HOST_LDLT)          # (the class solves the coarsest system on the host)
+    try:
+        eng.set_prolongations(solver.prolongation_matrices); eng.set_mass(mass); eng.set_system(lhs)
+        xe, it, res, _ = eng.solve(rhs, tol=1e-4, stop_type=2, max_iter=100)
+    finally:
+        eng.close()
+    assert res <= 1e-4 and len(solver.convergence) == it == int(solver.solver_timing["iterations"])
+    assert np.array_equal(x, xe)
+    default = gravomg.MultigridSolver(V, neigh, M, lower_bound=40, tolerance=1e-4, stopping_criteria=2, max_iter=100)
+    x22 = default.solve(lhs, rhs)
+    assert len(default.convergence) != it or not np.array_equal(x22, x)
+
+
 _FALLBACK_SCRIPT = r"""
 import io, os, sys, contextlib
 import numpy as np, scipy.sparse as sp

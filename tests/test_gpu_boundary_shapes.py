@@ -13,7 +13,7 @@ import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 from tests import problems
-from tests.parity_checks import check_block_sweeps, check_multicolor_gs, rel, timing_or_none
+from tests.parity_checks import SWITCHES, check_block_sweeps, check_multicolor_gs, engaged, rel, timing_or_none
 from tests.vcycle_model import VcycleModel
 
 pytestmark = pytest.mark.gpu
@@ -193,7 +193,7 @@ def test_smooth_residual_is_b_minus_Ax(case, cabi, oracle):
                 absA = abs(A)
                 for d in case.ds:
                     b = rng.standard_normal((A.shape[0], d)); x0 = rng.standard_normal((A.shape[0], d))
-                    for iters in (1, 2, 3):
+                    for iters in (1, 2, 3, 4, 5):
                         for from_zero in (False, True):
                             x, r = eng.smooth_residual(k, b, None if from_zero else x0, iters, from_zero=from_zero)
                             assert np.array_equal(x, eng.smooth(k, b, np.zeros_like(b) if from_zero else x0, iters))
@@ -302,22 +302,6 @@ def test_solve_matches_the_oracle(case, oracle):
         assert dx <= 20 * tol, d
 
 
-def _engaged(eng, switch):
-    """How much of the switched path ran, from the timing keys: heads enqueued ahead of the solve loop's decision, restrictions fused with
-    the next level's first pre-sweep, level-0 operators with 16-bit column codes, the code width of those read as uniform slices."""
-    def key(k):
-        return timing_or_none(eng, k) or 0.0      # (keys that only appear once their path has been set up or run)
-    if switch == "speculate_head":
-        return key("heads_enqueued")
-    if switch == "fuse_restrict_sweep":
-        return key("restrict_sweeps_fused")
-    ops = ("col16_l0", "col16_R_l0", "col16_P_l0")
-    if switch == "fine_col16":
-        return sum(key(k) for k in ops)
-    return sum(key(k + "_uniform_width") for k in ops)
-
-
-SWITCHES = ("speculate_head", "fuse_restrict_sweep", "uniform_slices", "fine_col16")
 # a catalogue shape on which each switch must engage (so that the bitwise comparison below compares two different launch sequences there)
 ENGAGES_ON = {"speculate_head": "A-chain64-L1", "fuse_restrict_sweep": "A-chain193-L3", "uniform_slices": "A-chain193-L1", "fine_col16": "D-coarsest3000"}
 
@@ -342,16 +326,16 @@ def test_switches_change_nothing(case, cabi, switch):
                 eng.load_problem(b, b)
                 hist = eng.run_cycles(3, 2).copy()
                 res[("run_cycles", d)] = (eng.fetch_solution().copy(), 3, hist, None)
-            engaged = _engaged(eng, switch)
+            ran = engaged(eng, switch)
             if not on:
-                assert engaged == 0, (switch, engaged)
+                assert ran == 0, (switch, ran)
             elif switch == "speculate_head":
                 eligible = eng.level_blocks(0) is None and eng.level_info(0)["n_colors"] >= 2
-                assert (engaged > 0) == eligible, (eligible, engaged)
+                assert (ran > 0) == eligible, (eligible, ran)
             elif switch == "fuse_restrict_sweep" and len(P.U) == 1:
-                assert engaged == 0, engaged
+                assert ran == 0, ran
             if on and case.name == ENGAGES_ON[switch]:
-                assert engaged > 0, (switch, case.name)
+                assert ran > 0, (switch, case.name)
             out.append(res)
         finally:
             eng.close()
@@ -392,6 +376,23 @@ def test_too_many_colours_on_level_0_is_refused_and_the_next_solve_is_a_state_er
         assert res <= 1e-8
     finally:
         eng.close()
+
+
+def test_fp32_twin_of_an_empty_block_csr_leaves_no_launch_error_behind(cabi):
+    """A level that is one block has no off-block entry: with block_lanes = 1, block_ep = 0 its block-CSR is empty, and the mixed-precision set-up
+    must not launch a conversion over 0 values -- a grid of 0 workgroups is refused, and the error it leaves on the thread was reported by the
+    NEXT gmg_set_system (GMG_ERR_HIP "invalid configuration argument"), whatever handle that was."""
+    (spec,) = [c[1] for c in CASES if c[0] == "A-chain193-L3"]
+    P = problems.synthetic_problem(**spec)
+    mix = _engine(cabi, P, block_lanes=1, block_ep=False, inner_precision=1)
+    try:
+        assert mix.level_info(2)["n"] == 24 and len(mix.level_blocks(2)[0]) == 2          # one block
+        x, it, res, _ = mix.solve(P.rhs[:, :3], tol=1e-8)
+        assert res <= 1e-8
+        for kw in (dict(), dict(block_lanes=1, block_ep=False, inner_precision=1)):
+            _engine(cabi, P, **kw).close()
+    finally:
+        mix.close()
 
 
 def test_empty_hierarchy_is_a_state_error(cabi):

@@ -11,8 +11,8 @@ from tests import problems
 pytestmark = pytest.mark.gpu
 
 
-def _engine(cabi, P, world):
-    eng = cabi.Engine(row_align=64 * world, use_graph=False)
+def _engine(cabi, P, world, pre=2, post=2):
+    eng = cabi.Engine(row_align=64 * world, use_graph=False, pre_iters=pre, post_iters=post)
     eng.set_prolongations(P.U); eng.set_mass(P.mass); eng.set_system(P.lhs)
     return eng
 
@@ -42,14 +42,26 @@ def test_world1_backend_matches_plain_engine(cabi, kind):
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_emulated_ranks_on_one_device(cabi, world):
+    _emulated_ranks(cabi, world)
+
+
+@pytest.mark.parametrize("pre,post", [(1, 1), (0, 2)])
+def test_emulated_ranks_on_one_device_at_other_sweep_counts(cabi, pre, post):
+    """The same lockstep with pre_iters / post_iters other than 2 + 2: the level-0 sweeps are counted here, the coarse cycle below them takes
+    the counts from the engine's configuration (gmg_dist_coarse_cycle) -- as gravo_mg_amd/dist.py drives it."""
+    _emulated_ranks(cabi, 2, pre, post)
+
+
+def _emulated_ranks(cabi, world, pre=2, post=2):
     import torch
     from gravo_mg_amd.dist import EngineBackend
     P = problems.torus_problem(96, 80, "poisson", 30)
     d = P.rhs.shape[1]
     # single-rank reference with the SAME padded layout (row_align = 64*world), one handle doing everything
-    ref_eng = _engine(cabi, P, world)
+    ref_eng = _engine(cabi, P, world, pre, post)
     ref = EngineBackend(ref_eng, d, 0, 1)          # world=1 on a 64*world-aligned layout is valid
-    bes = [EngineBackend(_engine(cabi, P, world), d, r, world) for r in range(world)]
+    bes = [EngineBackend(_engine(cabi, P, world, pre, post), d, r, world) for r in range(world)]
+    assert (ref.pre_iters, ref.post_iters) == (pre, post)
     cb, n_pad, C = bes[0].color_begin, bes[0].n_pad, len(bes[0].color_begin) - 1
     for b in bes + [ref]:
         b.load(P.rhs, P.rhs)
@@ -68,7 +80,7 @@ def test_emulated_ranks_on_one_device(cabi, world):
         torch.cuda.synchronize()
 
     def cycle_ranks():
-        for _ in range(2):
+        for _ in range(pre):
             for c in range(C):
                 for b in bes: b.smooth_color(c)
                 exchange("x", c)
@@ -77,16 +89,16 @@ def test_emulated_ranks_on_one_device(cabi, world):
         for b in bes: b.coarse_cycle()
         for b in bes: b.prolong_own()
         for c in range(C): exchange("x", c)
-        for _ in range(2):
+        for _ in range(post):
             for c in range(C):
                 for b in bes: b.smooth_color(c)
                 exchange("x", c)
 
     def cycle_ref():
-        for _ in range(2):
+        for _ in range(pre):
             for c in range(C): ref.smooth_color(c)
         ref.residual_own(); ref.coarse_cycle(); ref.prolong_own()
-        for _ in range(2):
+        for _ in range(post):
             for c in range(C): ref.smooth_color(c)
 
     for _ in range(3):

@@ -15,7 +15,7 @@ import pytest
 import scipy.sparse as sp
 
 from tests import problems
-from tests.parity_checks import check_block_sweeps as _check_block_sweeps, check_multicolor_gs, rel, timing_or_none
+from tests.parity_checks import check_block_sweeps as _check_block_sweeps, check_multicolor_gs, colour_permuted_hierarchy, rel, timing_or_none
 
 pytestmark = pytest.mark.gpu
 
@@ -199,20 +199,11 @@ def test_vcycle_matches_oracle_with_same_ordering(setup_exact, oracle):
     """One V-cycle (exact multicolour GS on every level) where the oracle is given the device's colour
     ordering on every level: same algebra, only floating-point summation order differs."""
     P, eng = setup_exact
-    L = len(P.U)
-    orders = []
-    for k in range(L):
-        n2o, _ = eng.level_ordering(k)
-        orders.append(n2o[n2o >= 0])
-    orders.append(np.arange(P.U[-1].shape[1]))
-    Up = [sp.csc_matrix(P.U[k].tocsr()[orders[k]][:, orders[k + 1]]) for k in range(L)]
-    lhs_p = sp.csc_matrix(P.lhs.tocsr()[orders[0]][:, orders[0]])
-    O = oracle.Hierarchy(Up, P.mass[orders[0]])
-    O.set_system(lhs_p)
+    O, order0 = colour_permuted_hierarchy(P, eng, oracle)
     x0 = P.rhs.copy()
     got = eng.vcycle(P.rhs, x0)
-    want_p = O.vcycle(P.rhs[orders[0]], x0[orders[0]])
-    want = np.empty_like(want_p); want[orders[0]] = want_p
+    want_p = O.vcycle(P.rhs[order0], x0[order0])
+    want = np.empty_like(want_p); want[order0] = want_p
     # backward-error style bound (insensitive to the 1/tau conditioning of the Poisson systems) ...
     import scipy.sparse.linalg as spla
     assert np.linalg.norm(P.lhs @ (got - want)) <= 1e-12 * spla.norm(P.lhs) * np.linalg.norm(want)

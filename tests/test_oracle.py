@@ -87,7 +87,7 @@ def test_galerkin_and_coarse_solve(P, oracle):
     assert np.linalg.norm(A @ e - rc) <= 1e-11 * (spla.norm(A) * np.linalg.norm(e))
 
 
-def _scipy_vcycle(As, Us, lu, b, x, k=0):
+def _scipy_vcycle(As, Us, lu, b, x, k=0, pre=2, post=2):
     def gs(A, b, x, it):
         DL = sp.tril(A, 0).tocsr()
         x = x.copy()
@@ -95,21 +95,58 @@ def _scipy_vcycle(As, Us, lu, b, x, k=0):
             for c in range(x.shape[1]):
                 x[:, c] += spla.spsolve_triangular(DL, b[:, c] - A @ x[:, c], lower=True)
         return x
-    x = gs(As[k], b, x, 2)
+    x = gs(As[k], b, x, pre)
     rc = Us[k].T @ (b - As[k] @ x)
     if k == len(Us) - 1:
         e = np.column_stack([lu.solve(rc[:, c]) for c in range(rc.shape[1])])
     else:
-        e = _scipy_vcycle(As, Us, lu, rc, np.zeros_like(rc), k + 1)
-    return gs(As[k], b, x + Us[k] @ e, 2)
+        e = _scipy_vcycle(As, Us, lu, rc, np.zeros_like(rc), k + 1, pre, post)
+    return gs(As[k], b, x + Us[k] @ e, post)
+
+
+def _levels(P):
+    As = [sp.csr_matrix(P.lhs)]
+    for U in P.U:
+        As.append(sp.csr_matrix(U.T @ As[-1] @ U))
+    return As, spla.splu(sp.csc_matrix(As[-1]))
+
+
+def _scipy_solve_count(P, As, lu, b, tol, max_iter, pre=2, post=2):
+    """The do-while loop (:1408-1419) around the scipy V-cycle: cycles run until the M-weighted residue (type 2) is <= tol."""
+    xs = b.copy(); its = 0
+    m = P.mass[:, None]
+    while True:
+        xs = _scipy_vcycle(As, P.U, lu, b, xs, 0, pre, post); its += 1
+        r = P.lhs @ xs - b
+        if np.sqrt(((r ** 2 * m).sum(0) / (b ** 2 * m).sum(0)).max()) <= tol or its >= max_iter:
+            return its
+
+
+SWEEP_COUNTS = [(0, 0), (0, 1), (1, 0), (1, 1), (3, 0), (0, 3), (3, 2), (5, 4)]
+
+
+@pytest.mark.parametrize("pre,post", SWEEP_COUNTS, ids=["%d+%d" % c for c in SWEEP_COUNTS])
+def test_vcycle_at_other_sweep_counts(P, oracle, pre, post):
+    """The V-cycle part of test_vcycle_and_solve_loop with pre_iters / post_iters other than 2 + 2 (the model the GPU tests compare against,
+    tests/vcycle_model.py, is assembled from this oracle with those counts): one cycle against the scipy restatement at the same backward
+    bound, and -- wherever there is smoothing -- the same number of cycles to 1e-4 as the scipy loop.  0 + 0 is the coarse-grid correction
+    alone: it does not contract, so only its cycle is pinned."""
+    As, lu = _levels(P)
+    O = oracle.Hierarchy(P.U, P.mass, pre_iters=pre, post_iters=post)
+    O.set_system(P.lhs)
+    b = P.rhs
+    x1 = _scipy_vcycle(As, P.U, lu, b, b.copy(), 0, pre, post)
+    got = O.vcycle(b, b.copy())
+    assert np.linalg.norm(P.lhs @ (got - x1)) <= 1e-11 * spla.norm(P.lhs) * np.linalg.norm(x1)
+    if (pre, post) != (0, 0):
+        x, it, res, conv = O.solve(b, tol=1e-4, stop_type=2, max_iter=100)
+        assert conv.shape == (it, 2)
+        assert it == _scipy_solve_count(P, As, lu, b, 1e-4, 100, pre, post)
 
 
 def test_vcycle_and_solve_loop(P, oracle):
     """multiGridVCycleGS (:1059-1088) and the do-while solve loop (:1408-1419)."""
-    As = [sp.csr_matrix(P.lhs)]
-    for U in P.U:
-        As.append(sp.csr_matrix(U.T @ As[-1] @ U))
-    lu = spla.splu(sp.csc_matrix(As[-1]))
+    As, lu = _levels(P)
     O = oracle.Hierarchy(P.U, P.mass)
     O.set_system(P.lhs)
     b = P.rhs

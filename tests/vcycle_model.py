@@ -9,7 +9,9 @@ the oracle's arithmetic plus the orderings the device reports:
     omega = 1 is the reference's update ``x_i <- (b_i - sum_{j != i} a_ij x_j) / a_ii`` applied colour by colour;
   * blocked levels: x += T^-1 (b - A x), T = D + strict lower triangle of A restricted to the block diagonal in device
     order (Jacobi between blocks, Gauss-Seidel inside), residual from the oracle, triangular solve from scipy;
-  * residual / restriction / prolongation / coarsest solve / Galerkin operators: the oracle's (gravomg_oracle.c).
+  * residual / restriction / prolongation / coarsest solve / Galerkin operators: the oracle's (gravomg_oracle.c);
+  * smoother="jacobi" (GMG_SMOOTHER_JACOBI, optional): every level x += jacobi_omega D^-1 (b - A x) per sweep, residual from the oracle --
+    no ordering of the device enters.
 
 A per-cycle comparison against this model checks the composition of the whole cycle (level order, zero initial coarse
 guess, which vectors feed which operator) to rounding -- also for iterations that do not contract.
@@ -22,7 +24,8 @@ import scipy.sparse.linalg as spla
 
 
 class VcycleModel:
-    def __init__(self, eng, U, mass, lhs, oracle, omega, pre=2, post=2):
+    def __init__(self, eng, U, mass, lhs, oracle, omega, pre=2, post=2, smoother="gs", jacobi_omega=0.67):
+        assert smoother in ("gs", "jacobi")
         self.oracle, self.omega, self.pre, self.post = oracle, float(omega), pre, post
         self.L = len(U)
         self.U = [sp.csc_matrix(u) for u in U]
@@ -31,6 +34,9 @@ class VcycleModel:
         self.A = [sp.csc_matrix(self.O.level_operator(k)) for k in range(self.L + 1)]
         self.sm = []
         for k in range(self.L):
+            if smoother == "jacobi":
+                self.sm.append(("jacobi", float(jacobi_omega), self.A[k].diagonal()))
+                continue
             blocks = eng.level_blocks(k)
             n2o, cb = eng.level_ordering(k)
             if blocks is None:
@@ -52,7 +58,10 @@ class VcycleModel:
         x = np.array(x, dtype=np.float64, copy=True)
         om = self.omega if (k == 0 and omega is None) else (1.0 if omega is None else omega)
         for _ in range(iters):
-            if kind == "colour":
+            if kind == "jacobi":
+                r = self.oracle.residual(self.A[k], b, x)
+                x = x + a * r / (c[:, None] if x.ndim == 2 else c)
+            elif kind == "colour":
                 for rows in a:
                     r = self.oracle.residual(self.A[k], b, x)
                     x[rows] += om * r[rows] / (c[rows][:, None] if x.ndim == 2 else c[rows])
