@@ -833,27 +833,8 @@ static int dist_smooth_color_impl(gmg_handle h, int c, const unsigned long long*
     if (l.ord.blocked) return fail(h, GMG_ERR_STATE, "level 0 is blocked: its sweep is a block sweep (gmg_p2p_cycles), not a colour sweep");
     int sb, se;
     own_range(h, c, sb, se);
-    const int d = h->loaded_d, ld = l.n_pad;
-    if (se > sb)
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
-            if (l.Aoff.c16_mode != 0 && plain_rows) {
-                DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color<double, D, C16 + 1, 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr,
-                                                  l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * ld, l.x + (size_t)c0 * ld, ld, sb, se, 1, h->cfg.gs_omega,
-                                                  l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg(), plain_rows)));
-            } else if (plain_rows) {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_color<double, D, 1, 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr,
-                                                  l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * ld, l.x + (size_t)c0 * ld, ld, sb, se, 1, h->cfg.gs_omega,
-                                                  (const unsigned*)nullptr, (const int*)nullptr, 0, plain_rows));
-            } else if (l.Aoff.c16_mode != 0) {       // (c16_sel: a rank whose share of the fine operators fits its memory-side cache reads them with ordinary loads)
-                DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color<double, D, C16 + 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr,
-                                                  l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * ld, l.x + (size_t)c0 * ld, ld, sb, se, 1, h->cfg.gs_omega,
-                                                  l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-            } else {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_color<double, D, 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr,
-                                                  l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * ld, l.x + (size_t)c0 * ld, ld, sb, se, 1, h->cfg.gs_omega));
-            }
-        }
+    // (c16_sel: a rank whose share of the fine operators fits its memory-side cache reads them with ordinary loads)
+    if (se > sb) for_col_chunks(h->loaded_d, [&](int c0, int dc) { launch_gs_color<double>(h, l, c0, dc, sb, se, h->cfg.gs_omega, plain_rows); });
     return GMG_OK;
 }
 int gmg_dist_smooth_color(gmg_handle h, int c) try { return dist_smooth_color_impl(h, c, nullptr); } GMG_CATCH_H
@@ -864,17 +845,10 @@ int gmg_dist_residual_own(gmg_handle h) try {
     int rc = dist_ready(h);
     if (rc) return rc;
     Level& l = h->lv[0];
-    const int d = h->loaded_d, ld = l.n_pad;
     for (int c = 0; c < dist_classes(l.ord); ++c) {
         int sb, se;
         own_range(h, c, sb, se);
-        if (se <= sb) continue;
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
-            DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::spmv_full<double, D, 1, 1, C16>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0,
-                                              h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * ld, l.x + (size_t)c0 * ld,
-                                              l.r + (size_t)c0 * ld, ld, sb, se, 1, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-        }
+        if (se > sb) launch_spmv_lpr<double, 1>(h, l, h->loaded_d, 1, l.b, l.x, l.r, sb, se);
     }
     return GMG_OK;
 } GMG_CATCH_H
@@ -907,17 +881,11 @@ int gmg_dist_prolong_own(gmg_handle h) try {
     if (rc) return rc;
     Level& l = h->lv[0];
     Level& cl = h->lv[1];
-    const int d = h->loaded_d;
     for (int c = 0; c < dist_classes(l.ord); ++c) {
         int sb, se;
         own_range(h, c, sb, se);
-        if (se <= sb) continue;
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
-            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::transfer<double, D, 1, 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.P.slice_ptr, l.P.col,
-                                              l.P.val, (const int*)nullptr, cl.x + (size_t)c0 * cl.n_pad, cl.n_pad, l.x + (size_t)c0 * l.n_pad, l.n_pad,
-                                              sb, se, 1));
-        }
+        // (quirk kept: C16 = 0 -- the 32-bit columns -- whatever l.P.c16_mode is)
+        if (se > sb) launch_prolong_add<double>(h, l, cl, h->loaded_d, cl.x, l.x, false, sb, se, 0);
     }
     return GMG_OK;
 } GMG_CATCH_H
@@ -932,8 +900,7 @@ static int dist_norm_launch(gmg_handle h, int type) {
     const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
     const int nc = dist_classes(l.ord);
     const int nblk = std::max(1, kNormBlocks / std::max(nc, 1));
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
+    for_col_chunks(d, [&](int c0, int dc) {
         for (int c = 0; c < nc; ++c) {
             int sb, se;
             own_range(h, c, sb, se);
@@ -943,7 +910,7 @@ static int dist_norm_launch(gmg_handle h, int type) {
         }
         hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, h->d_partials, nblk * nc, 2 * dc, h->d_norm + 2 * c0,
                            (unsigned long long*)nullptr, 0ull, 0);
-    }
+    });
     return GMG_OK;
 }
 

@@ -24,6 +24,20 @@ namespace {
         default: { constexpr int C16 = 0; __VA_ARGS__; } break; \
     }
 
+// a run-time flag as a compile-time one (kernel template arguments that are a bool, or an int / enum with two values in use)
+#define DISPATCH_FLAG(NAME, cond, ...)   \
+    { if (cond) { constexpr bool NAME = true; __VA_ARGS__; } else { constexpr bool NAME = false; __VA_ARGS__; } }
+
+// ... and an int with three values in use: NAME = A or B where v equals one of them, C otherwise
+#define DISPATCH_ONE_OF(NAME, v, A, B, C, ...)   \
+    { if ((v) == (A)) { constexpr int NAME = A; __VA_ARGS__; } else if ((v) == (B)) { constexpr int NAME = B; __VA_ARGS__; } else { constexpr int NAME = C; __VA_ARGS__; } }
+
+// the groups of <= 4 columns a kernel launch covers: f(first column, columns in the group)
+template <class F>
+inline void for_col_chunks(int d, F&& f) {
+    for (int c0 = 0; c0 < d; c0 += 4) f(c0, std::min(4, d - c0));
+}
+
 // Precision selector: the fp64 arrays, or their fp32 twins (same layout, same index arrays).
 template <class T> struct Prec;
 template <> struct Prec<double> {
@@ -75,37 +89,30 @@ bool fold_residual(gmg_handle, Level&, int, bool, int, int) { return false; }
 template <>
 bool fold_residual<double>(gmg_handle h, Level& l, int d, bool last_launch, int sb, int se) {
     if (!last_launch || !h->fuse_res_out || &l != &h->lv[0] || d > 4 || l.ord.n_colors < 2 || se != l.Aoff.n_slices || sb <= 0) return false;
-    if (h->il_r0 && d > 1) {
-        DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_residual<D, C16, (D > 1)>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream,
-                                         l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, h->fuse_res_out, l.n_pad, sb, se, h->cfg.gs_omega,
-                                         l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-    } else {
-        DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_residual<D, C16>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream,
-                                         l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, h->fuse_res_out, l.n_pad, sb, se, h->cfg.gs_omega,
-                                         l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-    }
+    DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), DISPATCH_FLAG(YI, h->il_r0, hipLaunchKernelGGL((gmgk::gs_color_residual<D, C16, (YI && D > 1)>), dim3(grid_for(se - sb)),
+                                     dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, h->fuse_res_out, l.n_pad, sb, se,
+                                     h->cfg.gs_omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg()))));
     h->fuse_res_from = sb;
     return true;
 }
 
 inline bool polled(gmg_handle h);
 
-// one colour launch of a sweep over level l (columns c0 .. c0 + dc); go: see gmgk::gs_color
+// over-relaxation on the finest level only (gmg_config::gs_omega)
 template <class T>
-void launch_gs_color(gmg_handle h, Level& l, int c0, int dc, int sb, int se, const int* go = nullptr) {
+T level_omega(gmg_handle h, const Level& l) { return &l == &h->lv[0] ? (T)h->cfg.gs_omega : (T)1.0; }
+
+// one colour launch of a sweep over level l (columns c0 .. c0 + dc), slices [sb, se); plain_rows (level 0, fp64: the hybrid smoother of the
+// distributed code), go: see gmgk::gs_color
+template <class T>
+void launch_gs_color(gmg_handle h, Level& l, int c0, int dc, int sb, int se, T omega, const unsigned long long* plain_rows = nullptr, const int* go = nullptr) {
     const int ld = l.n_pad;
-    const bool fine = &l == &h->lv[0];
-    const T omega = fine ? (T)h->cfg.gs_omega : (T)1.0;       // over-relaxation on the finest level only (gmg_config::gs_omega)
     T* x = Prec<T>::x(l);
     const T* b = Prec<T>::b(l);
-    if (fine && l.Aoff.c16_mode != 0) {           // FINE = 1 + C16 (c16_sel: 1 / 2 streamed, 3 / 4 a fine level that stays on the chip)
-        DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color<T, D, C16 + 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream,
-                                          l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
-                                          x + (size_t)c0 * ld, ld, sb, se, 1, omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg(), (const unsigned long long*)nullptr, go)));
-    } else if (fine) {
-        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_color<T, D, 1>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream,
-                                          l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
-                                          x + (size_t)c0 * ld, ld, sb, se, 1, omega, (const unsigned*)nullptr, (const int*)nullptr, 0, (const unsigned long long*)nullptr, go));
+    if (&l == &h->lv[0]) {           // FINE = 1 + C16 (c16_sel: 0 32-bit columns, 1 / 2 streamed codes, 3 / 4 a fine level that stays on the chip)
+        DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), DISPATCH_FLAG(OM, plain_rows != nullptr, hipLaunchKernelGGL((gmgk::gs_color<T, D, C16 + 1, (OM && sizeof(T) == 8)>),
+                                          dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l),
+                                          b + (size_t)c0 * ld, x + (size_t)c0 * ld, ld, sb, se, 1, omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg(), plain_rows, go))));
     } else {
         DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_color<T, D, 0>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0, h->stream,
                                           l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
@@ -130,7 +137,7 @@ inline bool head_eligible(gmg_handle h, int d) {
 inline void enqueue_head(gmg_handle h, int d) {
     Level& l = h->lv[0];
     const int c = first_color(l);
-    launch_gs_color<double>(h, l, 0, d, l.ord.color_begin[c] / 64, l.ord.color_begin[c + 1] / 64, reinterpret_cast<const int*>(h->d_watch + 1));
+    launch_gs_color<double>(h, l, 0, d, l.ord.color_begin[c] / 64, l.ord.color_begin[c + 1] / 64, level_omega<double>(h, l), nullptr, reinterpret_cast<const int*>(h->d_watch + 1));
     h->head_enqueued = true;
     h->timing["heads_enqueued"] += 1.0;
 }
@@ -143,17 +150,16 @@ void launch_gs_sweeps(gmg_handle h, Level& l, int d, int iters) {
     if (fine) h->head_enqueued = false;
     const int c_head = skip_head ? first_color(l) : -1;
     for (int it = 0; it < iters; ++it)
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
+        for_col_chunks(d, [&](int c0, int dc) {
             for (int c = 0; c < l.ord.n_colors; ++c) {
                 int sb = l.ord.color_begin[c] / 64, se = l.ord.color_begin[c + 1] / 64;
                 if (se <= sb) continue;
                 if (it == 0 && c0 == 0 && c == c_head) continue;
                 if (fold_norm<T>(h, l, d, it == iters - 1 && c == l.ord.n_colors - 1, sb, se)) continue;
                 if (fold_residual<T>(h, l, d, it == iters - 1 && c == l.ord.n_colors - 1, sb, se)) continue;
-                launch_gs_color<T>(h, l, c0, dc, sb, se);
+                launch_gs_color<T>(h, l, c0, dc, sb, se, level_omega<T>(h, l));
             }
-        }
+        });
 }
 
 template <class T>
@@ -162,20 +168,15 @@ void launch_jacobi_sweeps(gmg_handle h, Level& l, int d, int iters) {
     T* in = Prec<T>::x(l); T* out = Prec<T>::tmp(l);
     const T* b = Prec<T>::b(l);
     for (int it = 0; it < iters; ++it) {
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
+        for_col_chunks(d, [&](int c0, int dc) {
             DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::jacobi_sweep<T, D>), dim3(grid_for(l.Aoff.n_slices)), dim3(gmgk::kBlock), 0, h->stream,
                                               l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
                                               (in ? in + (size_t)c0 * ld : nullptr), out + (size_t)c0 * ld, ld, l.Aoff.n_slices, (T)h->cfg.jacobi_omega, 1));
-        }
+        });
         std::swap(in, out);
     }
     if (in != Prec<T>::x(l)) (void)hipMemcpyAsync(Prec<T>::x(l), in, sizeof(T) * (size_t)ld * d, hipMemcpyDeviceToDevice, h->stream);
 }
-
-// Launch geometry of the entry-parallel block sweep (kernels.hip.hpp::gs_block_ep): one block per workgroup.  (The kernel can also run as
-// persistent workgroups, grid < vgrid; measured in round 4 -- 8 .. 20 workgroups per compute unit -- the same or worse: profiles/r04/b_*.)
-inline int ep_persistent_grid(gmg_handle, int vgrid) { return vgrid; }
 
 // Does the entry-parallel block sweep of level l STREAM its operator (non-temporal loads)?  Yes when the operator's chunks (12 B per explicit,
 // 10 B per lower entry in fp64) are more than the memory-side cache (256 MB on MI355X) holds beside the cycle's vectors between two of the
@@ -195,25 +196,17 @@ void launch_block_sweep_range(gmg_handle h, Level& l, int d, const T* in, T* out
     // (begin_table / ncolors_table: an explicit list of nb blocks instead of a range -- entry-parallel sweep only, which reads
     // nothing but the first row of its block from the table)
     const int* blk_begin = begin_table ? begin_table : l.d_blk_begin + b0;
-    constexpr bool table_always = false;
     const int* blk_ncolors = ncolors_table ? ncolors_table : l.d_blk_ncolors + b0;
     if (nb <= 0) return;
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
+    for_col_chunks(d, [&](int c0, int dc) {
         if (l.use_ep) {
-            const int vgrid = (nb + 7) / 8 * 8;         // multiple of 8: the kernel's XCD-aware block map is a bijection onto [0, vgrid)
-            const int grid = ep_persistent_grid(h, vgrid);
-            if (ep_streams(l)) {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_block_ep<T, D, true>), dim3(grid), dim3(64), gmgk::ep_lds_bytes<T>(D, l.ep_cap_e, l.ep_cap_l), h->stream,
-                                                  ((begin_table || table_always) ? blk_begin : (const int*)nullptr), blk_ncolors, l.d_row_color, l.ep_ptr, l.ep_col, Prec<T>::epval(l), l.ee_ptr, l.ee_col,
-                                                  Prec<T>::eeval(l), Prec<T>::diag(l), b + (size_t)c0 * ld, (in ? in + (size_t)c0 * ld : nullptr),
-                                                  out + (size_t)c0 * ld, ld, l.ep_cap_e, l.ep_cap_l, nb, b0, vgrid, out_il));
-            } else {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_block_ep<T, D, false>), dim3(grid), dim3(64), gmgk::ep_lds_bytes<T>(D, l.ep_cap_e, l.ep_cap_l), h->stream,
-                                                  ((begin_table || table_always) ? blk_begin : (const int*)nullptr), blk_ncolors, l.d_row_color, l.ep_ptr, l.ep_col, Prec<T>::epval(l), l.ee_ptr, l.ee_col,
-                                                  Prec<T>::eeval(l), Prec<T>::diag(l), b + (size_t)c0 * ld, (in ? in + (size_t)c0 * ld : nullptr),
-                                                  out + (size_t)c0 * ld, ld, l.ep_cap_e, l.ep_cap_l, nb, b0, vgrid, out_il));
-            }
+            // one block per workgroup (persistent workgroups, grid < vgrid, measured the same or worse: profiles/r04/b_*); a multiple of 8: the
+            // kernel's XCD-aware block map is a bijection onto [0, vgrid).  The kernel takes its blocks from b0 on unless it is given a list
+            const int vgrid = (nb + 7) / 8 * 8;
+            DISPATCH_D(dc, DISPATCH_FLAG(STREAM, ep_streams(l), hipLaunchKernelGGL((gmgk::gs_block_ep<T, D, STREAM>), dim3(vgrid), dim3(64),
+                                              gmgk::ep_lds_bytes<T>(D, l.ep_cap_e, l.ep_cap_l), h->stream, begin_table, blk_ncolors, l.d_row_color, l.ep_ptr, l.ep_col,
+                                              Prec<T>::epval(l), l.ee_ptr, l.ee_col, Prec<T>::eeval(l), Prec<T>::diag(l), b + (size_t)c0 * ld,
+                                              (in ? in + (size_t)c0 * ld : nullptr), out + (size_t)c0 * ld, ld, l.ep_cap_e, l.ep_cap_l, nb, b0, vgrid, out_il)));
         } else if (l.use_bcsr && d > 1) {
             DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::gs_block_csrout<T, D, (D == 1 ? 32 : 24)>), dim3(nb), dim3(64),
                                               (size_t)l.bc_cap * (sizeof(T) + sizeof(int)) + (size_t)D * 64 * sizeof(T), h->stream, blk_begin,
@@ -231,7 +224,7 @@ void launch_block_sweep_range(gmg_handle h, Level& l, int d, const T* in, T* out
                                               l.Aout.col, Prec<T>::val(l.Aout), Prec<T>::diag(l), b + (size_t)c0 * ld, (in ? in + (size_t)c0 * ld : nullptr),
                                               out + (size_t)c0 * ld, ld));
         }
-    }
+    });
 }
 
 template <class T>
@@ -280,18 +273,11 @@ bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const int* begin
     const int grid = (nb + 7) / 8 * 8;
     const T* x_old = (const T*)h->sweep_prev;
     const T* x_new = Prec<T>::x(l);
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
-        if (ep_streams(l)) {
-            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::residual_delta_ep<T, D, true>), dim3(grid), dim3(64), gmgk::ep_lds_bytes<T>(0, l.ep_cap_e, 0), h->stream, begin_table,
-                                              l.ee_ptr, l.ee_col, Prec<T>::eeval(l), (x_old ? x_old + (size_t)c0 * ld : nullptr), x_new + (size_t)c0 * ld,
-                                              r + (size_t)c0 * ld, ld, nb));
-        } else {
-            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::residual_delta_ep<T, D, false>), dim3(grid), dim3(64), gmgk::ep_lds_bytes<T>(0, l.ep_cap_e, 0), h->stream, begin_table,
-                                              l.ee_ptr, l.ee_col, Prec<T>::eeval(l), (x_old ? x_old + (size_t)c0 * ld : nullptr), x_new + (size_t)c0 * ld,
-                                              r + (size_t)c0 * ld, ld, nb));
-        }
-    }
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_FLAG(STREAM, ep_streams(l), hipLaunchKernelGGL((gmgk::residual_delta_ep<T, D, STREAM>), dim3(grid), dim3(64),
+                                          gmgk::ep_lds_bytes<T>(0, l.ep_cap_e, 0), h->stream, begin_table, l.ee_ptr, l.ee_col, Prec<T>::eeval(l),
+                                          (x_old ? x_old + (size_t)c0 * ld : nullptr), x_new + (size_t)c0 * ld, r + (size_t)c0 * ld, ld, nb)));
+    });
     return true;
 }
 
@@ -308,60 +294,57 @@ void launch_smooth(gmg_handle h, Level& l, int d, int iters, bool from_zero = fa
     else launch_gs_sweeps<T>(h, l, d, iters);
 }
 
-// y = A x (mode 0) or y = b - A x (mode 1)
+// y = A x (mode 0) or y = b - A x (mode 1) on the slices [sb, se) of level l
+// y_il: the residual as an interleaved multi-vector (level 0, one lane per row, d = 2 .. 4: what the restriction gathers from)
 template <class T, int LPR>
-void launch_spmv_lpr(gmg_handle h, Level& l, int d, int mode, const T* b, const T* x, T* y, int n_slices = -1, bool y_il = false) {
+void launch_spmv_lpr(gmg_handle h, Level& l, int d, int mode, const T* b, const T* x, T* y, int sb, int se, bool y_il = false) {
     const int ld = l.n_pad;
-    if (n_slices < 0) n_slices = l.Aoff.n_slices;
-    if (y_il && mode == 1 && LPR == 1 && d > 1 && d <= 4) {        // residual as an interleaved multi-vector (level 0, d > 1: what the restriction gathers from)
-        DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::spmv_full<T, D, 1, 1, C16, (D > 1)>), dim3(grid_for(n_slices)), dim3(gmgk::kBlock), 0, h->stream,
-                                         l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b, x, y, ld, 0, n_slices, 1, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-        return;
-    }
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
-        if (LPR == 1 && l.Aoff.c16_mode != 0) {           // level 0 with 16-bit column codes
-            if (mode == 1) {
-                DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::spmv_full<T, D, 1, 1, C16>), dim3(grid_for(n_slices)), dim3(gmgk::kBlock), 0, h->stream,
-                                                  l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld, x + (size_t)c0 * ld,
-                                                  y + (size_t)c0 * ld, ld, 0, n_slices, 1, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-            } else {
-                DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::spmv_full<T, D, 0, 1, C16>), dim3(grid_for(n_slices)), dim3(gmgk::kBlock), 0, h->stream,
-                                                  l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), (const T*)nullptr, x + (size_t)c0 * ld,
-                                                  y + (size_t)c0 * ld, ld, 0, n_slices, 1, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-            }
-        } else if (mode == 1) {
-            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::spmv_full<T, D, 1, LPR>), dim3(grid_for(n_slices)), dim3(gmgk::kBlock), 0, h->stream,
-                                              l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld, x + (size_t)c0 * ld,
-                                              y + (size_t)c0 * ld, ld, 0, n_slices, 1));
-        } else {
-            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::spmv_full<T, D, 0, LPR>), dim3(grid_for(n_slices)), dim3(gmgk::kBlock), 0, h->stream,
-                                              l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), (const T*)nullptr, x + (size_t)c0 * ld,
-                                              y + (size_t)c0 * ld, ld, 0, n_slices, 1));
-        }
-    }
+    const bool il = y_il && mode == 1 && LPR == 1 && d > 1 && d <= 4;
+    for_col_chunks(d, [&](int c0, int dc) {
+        // (the 16-bit column codes belong to the one-lane-per-row layout of level 0: the quad layout has the plain instantiation only)
+        DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), DISPATCH_FLAG(RES, mode == 1, DISPATCH_FLAG(YI, il,
+                       hipLaunchKernelGGL((gmgk::spmv_full<T, D, (RES ? 1 : 0), LPR, (LPR == 1 ? C16 : 0), (YI && RES && LPR == 1 && D > 1)>), dim3(grid_for(se - sb)),
+                                          dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l),
+                                          (RES ? b + (size_t)c0 * ld : nullptr), x + (size_t)c0 * ld, y + (size_t)c0 * ld, ld, sb, se, 1, l.Aoff.col16,
+                                          l.Aoff.win_base, l.Aoff.c16_arg())))));
+    });
 }
+// the same on a LIST of slices (a rank's rows of a level partitioned by blocks), mode 1
+template <class T>
+void launch_spmv_list(gmg_handle h, Level& l, int d, const T* b, const T* x, T* y, const int* slices, int n_list) {
+    const int ld = l.n_pad;
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_FLAG(QUAD, l.Aoff.lpr == 4, hipLaunchKernelGGL((gmgk::spmv_full_list<T, D, 1, (QUAD ? 4 : 1)>), dim3(grid_for(n_list)), dim3(gmgk::kBlock), 0,
+                                          h->stream, l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld, x + (size_t)c0 * ld,
+                                          y + (size_t)c0 * ld, ld, slices, n_list)));
+    });
+}
+// the first n_slices slices (all of them by default)
 template <class T>
 void launch_spmv(gmg_handle h, Level& l, int d, int mode, const T* b, const T* x, T* y, int n_slices = -1, bool y_il = false) {
-    if (l.Aoff.lpr == 4) launch_spmv_lpr<T, 4>(h, l, d, mode, b, x, y, n_slices);
-    else launch_spmv_lpr<T, 1>(h, l, d, mode, b, x, y, n_slices, y_il);
+    if (n_slices < 0) n_slices = l.Aoff.n_slices;
+    if (l.Aoff.lpr == 4) launch_spmv_lpr<T, 4>(h, l, d, mode, b, x, y, 0, n_slices);
+    else launch_spmv_lpr<T, 1>(h, l, d, mode, b, x, y, 0, n_slices, y_il);
 }
 
-// coarse.b = U^T fine.r
+// coarse.b = U^T fine.r   (src_il: the source is an interleaved multi-vector, d = 2 .. 4)
 template <class T, int LPR>
 void launch_restrict_lpr(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, bool src_il = false) {
-    if (src_il && d > 1 && d <= 4) {
-        DISPATCH_D(d, DISPATCH_C16(fine.R.c16_sel(), hipLaunchKernelGGL((gmgk::transfer<T, D, 0, LPR, C16, (D > 1)>), dim3(grid_for(fine.R.n_slices)), dim3(gmgk::kBlock), 0,
-                                         h->stream, fine.R.slice_ptr, fine.R.col, Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, dst, coarse.n_pad, 0, fine.R.n_slices, 1,
-                                         fine.R.col16, fine.R.win_base, fine.R.c16_arg())));
-        return;
-    }
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
-        DISPATCH_D(dc, DISPATCH_C16(fine.R.c16_sel(), hipLaunchKernelGGL((gmgk::transfer<T, D, 0, LPR, C16>), dim3(grid_for(fine.R.n_slices)), dim3(gmgk::kBlock), 0,
+    const bool il = src_il && d > 1 && d <= 4;
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_C16(fine.R.c16_sel(), DISPATCH_FLAG(XI, il, hipLaunchKernelGGL((gmgk::transfer<T, D, 0, LPR, C16, (XI && D > 1)>), dim3(grid_for(fine.R.n_slices)),
+                                          dim3(gmgk::kBlock), 0, h->stream, fine.R.slice_ptr, fine.R.col, Prec<T>::val(fine.R), fine.R.row_of, src + (size_t)c0 * fine.n_pad,
+                                          fine.n_pad, dst + (size_t)c0 * coarse.n_pad, coarse.n_pad, 0, fine.R.n_slices, 1, fine.R.col16, fine.R.win_base, fine.R.c16_arg()))));
+    });
+}
+// the same on a LIST of the restriction's slices (a rank's rows of a coarse level partitioned by blocks; 32-bit columns, column-major source)
+template <class T>
+void launch_restrict_list(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, const int* slices, int n_list) {
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_FLAG(QUAD, fine.R.lpr == 4, hipLaunchKernelGGL((gmgk::transfer_list<T, D, 0, (QUAD ? 4 : 1)>), dim3(grid_for(n_list)), dim3(gmgk::kBlock), 0,
                                           h->stream, fine.R.slice_ptr, fine.R.col, Prec<T>::val(fine.R), fine.R.row_of, src + (size_t)c0 * fine.n_pad, fine.n_pad,
-                                          dst + (size_t)c0 * coarse.n_pad, coarse.n_pad, 0, fine.R.n_slices, 1, fine.R.col16, fine.R.win_base, fine.R.c16_arg())));
-    }
+                                          dst + (size_t)c0 * coarse.n_pad, coarse.n_pad, slices, n_list)));
+    });
 }
 template <class T>
 void launch_restrict(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, bool src_il = false) {
@@ -383,55 +366,49 @@ int restrict_sweep0_kind(gmg_handle h, const Level& fine, const Level& coarse, i
     if (!(coarse.use_bcsr && d > 1) && coarse.Ain.lpr == 4 && fine.R.c16_mode == 0 && !src_il && fine.R.n_slices * 16 == coarse.n_pad) return 2;
     return 0;
 }
+// blk_list / nb_list: the coarse blocks of ONE rank of a level partitioned by blocks instead of all of them (kind 1 only)
 template <class T>
-void launch_restrict_sweep0(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, bool src_il, int kind) {
-    const int nb = coarse.ord.n_blocks();
+void launch_restrict_sweep0(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, bool src_il, int kind, const int* blk_list = nullptr, int nb_list = 0) {
+    const int nb = blk_list ? nb_list : coarse.ord.n_blocks();
     if (kind == 2) {
         DISPATCH_D(d, hipLaunchKernelGGL((gmgk::gs_block4<T, D, 8, true>), dim3(nb), dim3(4 * h->cfg.block_rows), 0, h->stream, coarse.d_blk_begin, coarse.d_blk_ncolors,
                                          coarse.d_row_color, coarse.Ain.slice_ptr, coarse.ain_col16, Prec<T>::val(coarse.Ain), coarse.Aout.slice_ptr, coarse.Aout.col,
                                          Prec<T>::val(coarse.Aout), Prec<T>::diag(coarse), (const T*)nullptr, (const T*)nullptr, Prec<T>::tmp(coarse), coarse.n_pad,
                                          fine.R.slice_ptr, fine.R.col, Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, Prec<T>::b(coarse)));
-        h->first_sweep_fused = true;
         return;
     }
     const int vgrid = (nb + 7) / 8 * 8;
     const size_t lds_sweep = gmgk::ep_lds_bytes<T>(d, 0, coarse.ep_cap_l);
     const size_t lds = lds_sweep + (size_t)d * 64 * sizeof(T);
-    T* bdst = Prec<T>::b(coarse);
-    T* xdst = Prec<T>::tmp(coarse);               // (the result of a from-zero first sweep lives in tmp: launch_block_sweeps)
-#define GMG_RS0(XI_)                                                                                                                                        \
-    DISPATCH_D(d, DISPATCH_C16(fine.R.c16_sel(), {                                                                                                           \
-        if (ep_streams(coarse))                                                                                                                              \
-            hipLaunchKernelGGL((gmgk::restrict_sweep0<T, D, true, C16, (XI_ && D > 1)>), dim3(vgrid), dim3(256), lds, h->stream, fine.R.slice_ptr, fine.R.col,   \
-                               Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, fine.R.col16, fine.R.win_base, fine.R.c16_arg(), bdst, coarse.d_blk_ncolors,      \
-                               coarse.d_row_color, coarse.ep_ptr, coarse.ep_col, Prec<T>::epval(coarse), Prec<T>::diag(coarse), xdst, coarse.n_pad, nb, vgrid,       \
-                               (int)lds_sweep);                                                                                                              \
-        else                                                                                                                                                 \
-            hipLaunchKernelGGL((gmgk::restrict_sweep0<T, D, false, C16, (XI_ && D > 1)>), dim3(vgrid), dim3(256), lds, h->stream, fine.R.slice_ptr, fine.R.col,  \
-                               Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, fine.R.col16, fine.R.win_base, fine.R.c16_arg(), bdst, coarse.d_blk_ncolors,      \
-                               coarse.d_row_color, coarse.ep_ptr, coarse.ep_col, Prec<T>::epval(coarse), Prec<T>::diag(coarse), xdst, coarse.n_pad, nb, vgrid,       \
-                               (int)lds_sweep);                                                                                                              \
-    }))
-    if (src_il && d > 1) { GMG_RS0(1); } else { GMG_RS0(0); }
-#undef GMG_RS0
-    h->first_sweep_fused = true;
+    // (the result of a from-zero first sweep lives in tmp: launch_block_sweeps)
+    DISPATCH_D(d, DISPATCH_C16(fine.R.c16_sel(), DISPATCH_FLAG(STREAM, ep_streams(coarse), DISPATCH_FLAG(XI, src_il,
+                  hipLaunchKernelGGL((gmgk::restrict_sweep0<T, D, STREAM, C16, (XI && D > 1)>), dim3(vgrid), dim3(256), lds, h->stream, fine.R.slice_ptr, fine.R.col,
+                                     Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, fine.R.col16, fine.R.win_base, fine.R.c16_arg(), Prec<T>::b(coarse),
+                                     coarse.d_blk_ncolors, coarse.d_row_color, coarse.ep_ptr, coarse.ep_col, Prec<T>::epval(coarse), Prec<T>::diag(coarse),
+                                     Prec<T>::tmp(coarse), coarse.n_pad, nb, vgrid, (int)lds_sweep, blk_list)))));
 }
 
-// fine.x += U coarse.x   (U has <= 3 entries per row: always one lane per row)
+// fine.x += U coarse.x on the slices [sb, se) of the fine level (se < 0: all of them).  U has <= 3 entries per row: always one lane per row.
+// src_il: the source is an interleaved multi-vector (d = 2 .. 4); c16: the kernels' C16 argument (< 0: what the layout of U asks for)
 template <class T>
-void launch_prolong_add(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, bool src_il = false) {
-    if (src_il && d > 1 && d <= 4) {
-        DISPATCH_D(d, DISPATCH_C16(fine.P.c16_sel(), hipLaunchKernelGGL((gmgk::transfer<T, D, 1, 1, C16, (D > 1)>), dim3(grid_for(fine.P.n_slices)), dim3(gmgk::kBlock), 0,
-                                         h->stream, fine.P.slice_ptr, fine.P.col, Prec<T>::val(fine.P), (const int*)nullptr, src, coarse.n_pad, dst, fine.n_pad, 0, fine.P.n_slices, 1,
-                                         fine.P.col16, fine.P.win_base, fine.P.c16_arg())));
-        return;
-    }
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
-        DISPATCH_D(dc, DISPATCH_C16(fine.P.c16_sel(), hipLaunchKernelGGL((gmgk::transfer<T, D, 1, 1, C16>), dim3(grid_for(fine.P.n_slices)), dim3(gmgk::kBlock), 0,
-                                          h->stream, fine.P.slice_ptr, fine.P.col, Prec<T>::val(fine.P), (const int*)nullptr, src + (size_t)c0 * coarse.n_pad,
-                                          coarse.n_pad, dst + (size_t)c0 * fine.n_pad, fine.n_pad, 0, fine.P.n_slices, 1, fine.P.col16, fine.P.win_base, fine.P.c16_arg())));
-    }
+void launch_prolong_add(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, bool src_il = false, int sb = 0, int se = -1, int c16 = -1) {
+    const bool il = src_il && d > 1 && d <= 4;
+    if (se < 0) se = fine.P.n_slices;
+    if (c16 < 0) c16 = fine.P.c16_sel();
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_C16(c16, DISPATCH_FLAG(XI, il, hipLaunchKernelGGL((gmgk::transfer<T, D, 1, 1, C16, (XI && D > 1)>), dim3(grid_for(se - sb)), dim3(gmgk::kBlock), 0,
+                                          h->stream, fine.P.slice_ptr, fine.P.col, Prec<T>::val(fine.P), (const int*)nullptr, src + (size_t)c0 * coarse.n_pad, coarse.n_pad,
+                                          dst + (size_t)c0 * fine.n_pad, fine.n_pad, sb, se, 1, fine.P.col16, fine.P.win_base, fine.P.c16_arg()))));
+    });
+}
+// the same on a LIST of the prolongation's slices (32-bit columns, column-major source)
+template <class T>
+void launch_prolong_add_list(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, const int* slices, int n_list) {
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::transfer_list<T, D, 1, 1>), dim3(grid_for(n_list)), dim3(gmgk::kBlock), 0, h->stream, fine.P.slice_ptr, fine.P.col,
+                                          Prec<T>::val(fine.P), (const int*)nullptr, src + (size_t)c0 * coarse.n_pad, coarse.n_pad, dst + (size_t)c0 * fine.n_pad,
+                                          fine.n_pad, slices, n_list));
+    });
 }
 
 // Polled completion.  Slot 0: residual-norm sums in h_norm; slot 1: the coarsest right-hand side in h_pinned.
@@ -495,13 +472,12 @@ int launch_norm(gmg_handle h, int d, int type) {
     const int n_slices = folded ? l.ord.color_begin[l.ord.n_colors - 1] / 64 : l.Aoff.n_slices;
     const int nblk = norm_grid(n_slices);                // one slice per wave, like the residual SpMV; one partial per block of 16
     const bool poll = polled(h);
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
+    for_col_chunks(d, [&](int c0, int dc) {
         DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices<D, 0, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
                                           l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * l.n_pad, l.x + (size_t)c0 * l.n_pad, w,
                                           l.n_pad, n_slices, (float*)nullptr, h->d_partials, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
         launch_reduce(h, nblk + folded, dc, c0, c0 + 4 >= d);
-    }
+    });
     if (!poll) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
 }
@@ -687,7 +663,7 @@ void restrict_into(gmg_handle h, int k, int d, bool il) {
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
     const int fused = (k + 1 < h->L && smooth_from_zero_ok(h, c, h->cfg.pre_iters)) ? restrict_sweep0_kind<T>(h, l, c, d, il) : 0;
-    if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); }
+    if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); h->first_sweep_fused = true; }
     else launch_restrict<T>(h, l, c, d, Prec<T>::r(l), Prec<T>::b(c), il);
 }
 
@@ -758,9 +734,8 @@ inline void launch_cvt(gmg_handle h, const float* src, double* dst, size_t n) {
 #ifndef GMG_SYMV_ROWS
 #define GMG_SYMV_ROWS 0
 #endif
-inline int symv_env(const char* name) { const char* v = std::getenv(name); return v ? std::atoi(v) : 0; }
 inline int symv_rows(int n, int d) {
-    static const int forced = symv_env("GMG_SYMV_ROWS");      // (measurement: scripts/symv_sweep.py)
+    const int forced = EnvSwitches::get().symv_rows;      // (measurement: scripts/symv_sweep.py)
     if (forced == 1 || forced == 2 || forced == 4) return forced;
     if (GMG_SYMV_ROWS > 0) return GMG_SYMV_ROWS;       // (A/B builds)
     // with 16-byte loads (dense_symv_v2; profiles/r06/symv_rows_loads_sweep.txt): one row per wave while the level is small (n_L = 1 929: 11.8 us at
@@ -770,7 +745,7 @@ inline int symv_rows(int n, int d) {
 }
 // strides of 64 columns a lane loads per trip (dense_symv's U)
 inline int symv_strides(int n, int d, int rows) {
-    static const int forced = symv_env("GMG_SYMV_STRIDES");
+    const int forced = EnvSwitches::get().symv_strides;
     if (forced == 2 || forced == 4 || forced == 8) return forced;
     (void)n; (void)d; (void)rows;
     return 4;                                          // (2 / 4 / 8 measured: within the noise of each other except four rows x two strides at 4 046: +3 us)
@@ -782,30 +757,23 @@ void enqueue_coarse_device(gmg_handle h, int d) {
     Level& c = h->lv[h->L];
     const size_t cnt = (size_t)c.n_pad * d;
     if (sizeof(T) == 4) launch_cvt(h, c.b32, c.b, cnt);
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
+    for_col_chunks(d, [&](int c0, int dc) {
         // rows per wave: the rows of a wave share the loads of the vectors (what bounds the product at d = 3 and at n_L beyond the L1's reach); a small
         // level keeps one row per wave -- it needs every wave it can get to cover the memory latency
         const int rows_per_wave = symv_rows(c.n, dc);
         const int per_block = gmgk::kWavesPerBlock * rows_per_wave;
         const dim3 grid((c.n + per_block - 1) / per_block);
         const int strides = symv_strides(c.n, dc, rows_per_wave);
-#define GMG_SYMV_LAUNCH(R, U) DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::dense_symv<D, R, U>), grid, dim3(gmgk::kBlock), 0, h->stream, h->d_ainv, c.n, h->ainv_ld, c.b + (size_t)c0 * c.n_pad, c.x + (size_t)c0 * c.n_pad, c.n_pad))
-#define GMG_SYMV_U(R) do { if (strides >= 8) { GMG_SYMV_LAUNCH(R, 8); } else if (strides >= 4) { GMG_SYMV_LAUNCH(R, 4); } else { GMG_SYMV_LAUNCH(R, 2); } } while (0)
-        static const char* v2_env = std::getenv("GMG_SYMV_V2");
-        const bool v2 = v2_env ? std::atoi(v2_env) != 0 : true;
-        if (v2 && rows_per_wave <= 2 && (h->ainv_ld & 1) == 0 && (c.n_pad & 1) == 0) {
-            if (rows_per_wave == 4) { DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::dense_symv_v2<D, 4, 2>), grid, dim3(gmgk::kBlock), 0, h->stream, h->d_ainv, c.n, h->ainv_ld, c.b + (size_t)c0 * c.n_pad, c.x + (size_t)c0 * c.n_pad, c.n_pad)); }
-            else if (rows_per_wave == 2) { DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::dense_symv_v2<D, 2, 2>), grid, dim3(gmgk::kBlock), 0, h->stream, h->d_ainv, c.n, h->ainv_ld, c.b + (size_t)c0 * c.n_pad, c.x + (size_t)c0 * c.n_pad, c.n_pad)); }
-            else { DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::dense_symv_v2<D, 1, 2>), grid, dim3(gmgk::kBlock), 0, h->stream, h->d_ainv, c.n, h->ainv_ld, c.b + (size_t)c0 * c.n_pad, c.x + (size_t)c0 * c.n_pad, c.n_pad)); }
-            continue;
+        const double* b = c.b + (size_t)c0 * c.n_pad;
+        double* x = c.x + (size_t)c0 * c.n_pad;
+        if (EnvSwitches::get().symv_v2 && rows_per_wave <= 2 && (h->ainv_ld & 1) == 0 && (c.n_pad & 1) == 0) {      // 16-byte loads: one or two rows per wave
+            DISPATCH_D(dc, DISPATCH_FLAG(TWO, rows_per_wave == 2, hipLaunchKernelGGL((gmgk::dense_symv_v2<D, (TWO ? 2 : 1), 2>), grid, dim3(gmgk::kBlock), 0, h->stream,
+                                              h->d_ainv, c.n, h->ainv_ld, b, x, c.n_pad)));
+        } else {
+            DISPATCH_D(dc, DISPATCH_ONE_OF(R, rows_per_wave, 4, 2, 1, DISPATCH_ONE_OF(U, strides, 8, 4, 2, hipLaunchKernelGGL((gmgk::dense_symv<D, R, U>), grid,
+                                              dim3(gmgk::kBlock), 0, h->stream, h->d_ainv, c.n, h->ainv_ld, b, x, c.n_pad))));
         }
-        if (rows_per_wave == 4) GMG_SYMV_U(4);
-        else if (rows_per_wave == 2) GMG_SYMV_U(2);
-        else GMG_SYMV_U(1);
-#undef GMG_SYMV_U
-#undef GMG_SYMV_LAUNCH
-    }
+    });
     if (sizeof(T) == 4) launch_cvt(h, c.x, c.x32, cnt);
 }
 
@@ -933,13 +901,12 @@ int launch_residual_to_f32(gmg_handle h, int d, int type) {
     Level& l = h->lv[0];
     const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
     const int nblk = norm_grid(l.Aoff.n_slices);
-    for (int c0 = 0; c0 < d; c0 += 4) {
-        int dc = std::min(4, d - c0);
+    for_col_chunks(d, [&](int c0, int dc) {
         DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices<D, 1, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
                                           l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * l.n_pad, l.x + (size_t)c0 * l.n_pad, w, l.n_pad,
                                           l.Aoff.n_slices, l.b32 + (size_t)c0 * l.n_pad, h->d_partials, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
         launch_reduce(h, nblk, dc, c0, c0 + 4 >= d);
-    }
+    });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
 }

@@ -160,10 +160,8 @@ int coll_exchange(gmg_handle h, int kind, double* vec, int ld) {
     int rc = coll_all_gather(h, kind, parity);
     if (rc) return rc;
     const int u = kind * 2 + parity;
-    if (cb.unpack_n[u] > 0) {
-        if (cb.mode == 2) hipLaunchKernelGGL(gmgk::coll_unpack<true>, dim3(cb.unpack_n[u] * B), dim3(256), 0, h->stream, cb.d_segs + cb.unpack_at[u], cb.unpack_n[u], (const double*)cb.recv, vec, ld, p->d, B);
-        else hipLaunchKernelGGL(gmgk::coll_unpack<false>, dim3(cb.unpack_n[u] * B), dim3(256), 0, h->stream, cb.d_segs + cb.unpack_at[u], cb.unpack_n[u], (const double*)cb.recv, vec, ld, p->d, B);
-    }
+    if (cb.unpack_n[u] > 0)
+        DISPATCH_FLAG(SYS, cb.mode == 2, hipLaunchKernelGGL(gmgk::coll_unpack<SYS>, dim3(cb.unpack_n[u] * B), dim3(256), 0, h->stream, cb.d_segs + cb.unpack_at[u], cb.unpack_n[u], (const double*)cb.recv, vec, ld, p->d, B));
     return GMG_OK;
 }
 
@@ -203,13 +201,8 @@ bool p2p_smooth_color_folded(gmg_handle h, int c) {
     pt.seq = p->seq; pt.err = p->d_err; pt.fenced = p->fenced ? 1 : 0;
     const int ld = l.n_pad;
     const dim3 grid(grid_for(se - sb)), block(gmgk::kBlock);
-    if (l.Aoff.c16_mode != 0) {
-        DISPATCH_D(p->d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_push<D, C16 + 1>), grid, block, 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, ld, sb, se,
-                                            h->cfg.gs_omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg(), pt)));
-    } else {
-        DISPATCH_D(p->d, hipLaunchKernelGGL((gmgk::gs_color_push<D, 1>), grid, block, 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, ld, sb, se,
-                                            h->cfg.gs_omega, (const unsigned*)nullptr, (const int*)nullptr, 0, pt));
-    }
+    DISPATCH_D(p->d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_push<D, C16 + 1>), grid, block, 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, ld, sb, se,
+                                        h->cfg.gs_omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg(), pt)));
     return true;
 }
 
@@ -831,50 +824,13 @@ int p2p_coarse_cycle_sharded(gmg_handle h) {
     // :1069 on my rows of level 1 -- together with the first pre-sweep of my blocks where the layouts allow it (restrict_sweep0 over this rank's
     // block list: a workgroup's four restriction slices are one block; same bits as the two launches)
     const bool fuse = from_zero && p->n_rsl > 0 && d <= 4 && restrict_sweep0_kind<double>(h, l0, l1, d, false) == 1 && l0.R.lpr == 4 && p->n_rsl == 4 * (int)p->own_blocks[p->rank].size();
-    if (fuse) {
-        const int nbk = (int)p->own_blocks[p->rank].size();
-        const int vgrid = (nbk + 7) / 8 * 8;
-        const size_t lds_sweep = gmgk::ep_lds_bytes<double>(d, 0, l1.ep_cap_l);
-        const size_t lds = lds_sweep + (size_t)d * 64 * sizeof(double);
-        DISPATCH_D(d, DISPATCH_C16(l0.R.c16_sel(), {
-            if (ep_streams(l1))
-                hipLaunchKernelGGL((gmgk::restrict_sweep0<double, D, true, C16, 0>), dim3(vgrid), dim3(256), lds, h->stream, l0.R.slice_ptr, l0.R.col, l0.R.val, l0.R.row_of, l0.r, l0.n_pad,
-                                   l0.R.col16, l0.R.win_base, l0.R.c16_arg(), l1.b, l1.d_blk_ncolors, l1.d_row_color, l1.ep_ptr, l1.ep_col, l1.ep_val, l1.diag, l1.tmp, l1.n_pad, nbk, vgrid,
-                                   (int)lds_sweep, (const int*)p->d_own_blocks);
-            else
-                hipLaunchKernelGGL((gmgk::restrict_sweep0<double, D, false, C16, 0>), dim3(vgrid), dim3(256), lds, h->stream, l0.R.slice_ptr, l0.R.col, l0.R.val, l0.R.row_of, l0.r, l0.n_pad,
-                                   l0.R.col16, l0.R.win_base, l0.R.c16_arg(), l1.b, l1.d_blk_ncolors, l1.d_row_color, l1.ep_ptr, l1.ep_col, l1.ep_val, l1.diag, l1.tmp, l1.n_pad, nbk, vgrid,
-                                   (int)lds_sweep, (const int*)p->d_own_blocks);
-        }));
-    } else if (p->n_rsl > 0)
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
-            if (l0.R.lpr == 4) {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::transfer_list<double, D, 0, 4>), dim3(grid_for(p->n_rsl)), dim3(gmgk::kBlock), 0, h->stream, l0.R.slice_ptr,
-                                                  l0.R.col, l0.R.val, l0.R.row_of, l0.r + (size_t)c0 * l0.n_pad, l0.n_pad, l1.b + (size_t)c0 * l1.n_pad, l1.n_pad,
-                                                  p->d_rsl, p->n_rsl));
-            } else {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::transfer_list<double, D, 0, 1>), dim3(grid_for(p->n_rsl)), dim3(gmgk::kBlock), 0, h->stream, l0.R.slice_ptr,
-                                                  l0.R.col, l0.R.val, l0.R.row_of, l0.r + (size_t)c0 * l0.n_pad, l0.n_pad, l1.b + (size_t)c0 * l1.n_pad, l1.n_pad,
-                                                  p->d_rsl, p->n_rsl));
-            }
-        }
+    // (quirk kept: the source is column-major, XI = 0, at every d)
+    if (fuse) launch_restrict_sweep0<double>(h, l0, l1, d, l0.r, false, 1, p->d_own_blocks, (int)p->own_blocks[p->rank].size());
+    else if (p->n_rsl > 0) launch_restrict_list<double>(h, l0, l1, d, l0.r, l1.b, p->d_rsl, p->n_rsl);
     if (!from_zero) HIPCHK(hipMemsetAsync(l1.x, 0, sizeof(double) * (size_t)l1.n_pad * d, h->stream));       // :1072-1073
     if ((rc = p2p_smooth_level1(h, h->cfg.pre_iters, from_zero, fuse))) return rc;        // :1063
     const bool from_sweep = launch_residual_delta<double>(h, l1, d, l1.r, p->d_own_begin, (int)p->own_blocks[p->rank].size());      // :1066 on my rows ...
-    if (!from_sweep && p->n_asl > 0)                                                  // ... or with the residual SpMV
-        for (int c0 = 0; c0 < d; c0 += 4) {
-            int dc = std::min(4, d - c0);
-            if (l1.Aoff.lpr == 4) {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::spmv_full_list<double, D, 1, 4>), dim3(grid_for(p->n_asl)), dim3(gmgk::kBlock), 0, h->stream, l1.Aoff.slice_ptr,
-                                                  l1.Aoff.col, l1.Aoff.val, l1.diag, l1.b + (size_t)c0 * l1.n_pad, l1.x + (size_t)c0 * l1.n_pad,
-                                                  l1.r + (size_t)c0 * l1.n_pad, l1.n_pad, p->d_asl, p->n_asl));
-            } else {
-                DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::spmv_full_list<double, D, 1, 1>), dim3(grid_for(p->n_asl)), dim3(gmgk::kBlock), 0, h->stream, l1.Aoff.slice_ptr,
-                                                  l1.Aoff.col, l1.Aoff.val, l1.diag, l1.b + (size_t)c0 * l1.n_pad, l1.x + (size_t)c0 * l1.n_pad,
-                                                  l1.r + (size_t)c0 * l1.n_pad, l1.n_pad, p->d_asl, p->n_asl));
-            }
-        }
+    if (!from_sweep && p->n_asl > 0) launch_spmv_list<double>(h, l1, d, l1.b, l1.x, l1.r, p->d_asl, p->n_asl);      // ... or with the residual SpMV
     if ((rc = p2p_exchange(h, C + 4, l1.r, l1.n_pad))) return rc;                      // everybody's rows -> complete r1 on every rank
     h->first_sweep_fused = false;
     restrict_into<double>(h, 1, d, false);                                            // :1069, replicated from here down (+ level 2's first sweep where fused)
@@ -882,12 +838,7 @@ int p2p_coarse_cycle_sharded(gmg_handle h) {
     if (h->coarse_device) enqueue_coarse_device<double>(h, d);
     else if ((rc = coarse_host_begin<double>(h, d))) return rc;       // the host half is served at the end of the cycle's enqueue (p2p_vcycle)
     enqueue_up<double>(h, d, 2);
-    for (int c0 = 0; c0 < d && p->n_psl > 0; c0 += 4) {                               // :1082 into my rows of level 1
-        int dc = std::min(4, d - c0);
-        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::transfer_list<double, D, 1, 1>), dim3(grid_for(p->n_psl)), dim3(gmgk::kBlock), 0, h->stream, l1.P.slice_ptr, l1.P.col,
-                                          l1.P.val, (const int*)nullptr, h->lv[2].x + (size_t)c0 * h->lv[2].n_pad, h->lv[2].n_pad, l1.x + (size_t)c0 * l1.n_pad,
-                                          l1.n_pad, p->d_psl, p->n_psl));
-    }
+    if (p->n_psl > 0) launch_prolong_add_list<double>(h, l1, h->lv[2], d, h->lv[2].x, l1.x, p->d_psl, p->n_psl);      // :1082 into my rows of level 1
     if ((rc = p2p_exchange(h, C + 3, l1.x, l1.n_pad))) return rc;
     return p2p_smooth_level1(h, h->cfg.post_iters, false);                            // :1085; leaves x1 current on my rows + halo
 }
@@ -958,8 +909,7 @@ int gmg_p2p_cycles(gmg_handle h, int n_cycles, int stop_type, double* residues) 
             HIPCHK(hipMemcpyAsync(cb.send, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToDevice, h->stream));
             if ((rc = coll_all_gather(h, kind, parity))) return rc;
             const double* gathered = cb.recv + (size_t)parity * p->world * cb.max_chunk;
-            if (cb.mode == 2) hipLaunchKernelGGL(gmgk::coll_sum_ranks<true>, dim3(1), dim3(64), 0, h->stream, gathered, cb.chunk[kind], p->world, p->rank, (const double*)h->d_norm, 2 * d, p->d_sums);
-            else hipLaunchKernelGGL(gmgk::coll_sum_ranks<false>, dim3(1), dim3(64), 0, h->stream, gathered, cb.chunk[kind], p->world, p->rank, (const double*)h->d_norm, 2 * d, p->d_sums);
+            DISPATCH_FLAG(SYS, cb.mode == 2, hipLaunchKernelGGL(gmgk::coll_sum_ranks<SYS>, dim3(1), dim3(64), 0, h->stream, gathered, cb.chunk[kind], p->world, p->rank, (const double*)h->d_norm, 2 * d, p->d_sums));
             d_result = p->d_sums;
         } else if (np > 0) {
             const int kind = C + 2, parity = (int)(p->kind_count[kind]++ & 1);

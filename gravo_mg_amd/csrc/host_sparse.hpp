@@ -91,6 +91,9 @@ struct Compressed {
 //   GMG_PUBLISH_FENCED=1    device -> pinned host publications (residual sums, coarsest right-hand side) behind a system-scope release fence
 //   GMG_P2P_SHARED_DEVICE=1 gmg_p2p_connect accepts ranks that sit on the SAME device (functional tests on a one-GPU box; exchange kernels of
 //                           such ranks wait for each other on one device: milliseconds per exchange, never a measurement)
+//   GMG_SYMV_ROWS=1|2|4     rows per wave of the coarsest level's dense product (default: by the level's size, engine_cycle.hip.hpp::symv_rows)
+//   GMG_SYMV_STRIDES=2|4|8  strides of 64 columns a lane of that product loads per trip (default 4)
+//   GMG_SYMV_V2=0           that product with 8-byte instead of 16-byte loads (measurement: scripts/symv_sweep.py)
 // Everything else that used to be an A/B switch is either a gmg_config field or gone.
 struct EnvSwitches {
     int host_threads = 0, local_world = 0, ldlt_threads = 0;
@@ -98,6 +101,8 @@ struct EnvSwitches {
     bool block_smallest_last = true;       // GMG_BLOCK_COLOURING=bfs: in-block colouring in breadth-first instead of smallest-last order (host_plan.hpp::make_block_ordering)
     double p2p_timeout_s = 0.0;
     bool p2p_fence_free = false, publish_fenced = false, p2p_shared_device = false;
+    int symv_rows = 0, symv_strides = 0;   // 0: the engine's choice
+    bool symv_v2 = true;
     static const EnvSwitches& get() {
         static const EnvSwitches v = [] {
             EnvSwitches e;
@@ -113,6 +118,9 @@ struct EnvSwitches {
             e.p2p_fence_free = num("GMG_P2P_FENCE_FREE") > 0;
             e.publish_fenced = num("GMG_PUBLISH_FENCED") > 0;
             e.p2p_shared_device = num("GMG_P2P_SHARED_DEVICE") > 0;
+            e.symv_rows = std::max(0, (int)num("GMG_SYMV_ROWS"));
+            e.symv_strides = std::max(0, (int)num("GMG_SYMV_STRIDES"));
+            e.symv_v2 = (int)num("GMG_SYMV_V2") != 0;
             return e;
         }();
         return v;
