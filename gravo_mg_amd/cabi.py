@@ -140,6 +140,9 @@ SIGNATURES = {
 INTERNAL_SIGNATURES = {
     "gmg_debug_sell_info": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "gmg_debug_sell_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _dp, _ip, _dp]),
+    "gmg_debug_select_parents": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.c_int,
+                                           C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), _ip, _dp]),
+    "gmg_hierarchy_debug_row_kinds": (C.c_int, [_vp, C.c_int, _ip]),
     "gmg_host_galerkin": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp]),
     "gmg_host_plan_level": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_ubyte)]),
@@ -262,7 +265,7 @@ class Hierarchy:
         l.gmg_hierarchy_options_default(C.byref(opt))
         opt.ratio, opt.lower_bound, opt.check_voronoi, opt.nested = float(ratio), int(lower_bound), int(bool(check_voronoi)), int(bool(nested))
         opt.sampling, opt.weighting, opt.debug, opt.full_clustering = int(sampling), int(weighting), int(bool(debug)), int(bool(full_clustering))
-        opt.use_device = int(bool(use_device))
+        opt.use_device = int(use_device)           # 0 host only, 1 default, 2 every level on the device (test setting)
         self._h = _vp()
         rc = l.gmg_hierarchy_build(_pd(pos), pos.shape[0], _pi(neigh), neigh.shape[1], C.byref(opt), C.byref(self._h))
         if rc:
@@ -297,6 +300,13 @@ class Hierarchy:
         if cnt.value:
             self.fine_order = np.empty(cnt.value, np.int32)
             l.gmg_hierarchy_get_fine_order(self._h, _pi(self.fine_order), C.byref(cnt))
+
+    def row_kinds(self, k: int) -> np.ndarray:
+        """Rows of U_k by kind: containing triangle / edge / closest three / single or one neighbour (gmg_hierarchy_debug_row_kinds)."""
+        out = np.zeros(4, np.int32)
+        if lib().gmg_hierarchy_debug_row_kinds(self._h, int(k), _pi(out)):
+            raise GmgError(GMG_ERR_INVALID, "gmg_hierarchy_debug_row_kinds failed")
+        return out
 
     def timing(self, key: str) -> float:
         out = C.c_double()

@@ -1121,6 +1121,7 @@ int gmg_hierarchy_build(const double* pos, int n, const int* neigh, int K, const
     // the per-point selection stage runs on the GPU when there is one (same bits as the host loop; gmg_hierarchy_options::use_device = 0: host only)
     {
         int ndev = 0;
+        if (o.use_device == 2) ho.device_select_min_points = 0;      // test setting: every level on the device, whatever its size
         if (o.use_device != 0 && n >= ho.device_select_min_points && hipGetDeviceCount(&ndev) == hipSuccess && ndev > 0) ho.device_select = hierarchy_select_on_device;
         else (void)hipGetLastError();
     }
@@ -1226,6 +1227,44 @@ int gmg_hierarchy_get_fine_order(gmg_hierarchy hh, int* out, int* count) try {
     if (!hh || !count) return GMG_ERR_INVALID;
     *count = (int)hh->fine_order.size();
     if (out && !hh->fine_order.empty()) std::memcpy(out, hh->fine_order.data(), sizeof(int) * hh->fine_order.size());
+    return GMG_OK;
+} GMG_CATCH_0
+
+int gmg_hierarchy_debug_row_kinds(gmg_hierarchy hh, int k, int* out) try {
+    if (!hh || !out || k < 0 || k >= (int)hh->res.row_kinds.size()) return GMG_ERR_INVALID;
+    for (int z = 0; z < 4; ++z) out[z] = hh->res.row_kinds[k][z];
+    return GMG_OK;
+} GMG_CATCH_0
+
+// Test access to the per-point parent selection of one level (gravomg_hip_internal.h): the host routine, the device stage through
+// hierarchy_select_on_device -- the builder's own upload / launch / download -- or the builder's combination of the two.
+int gmg_debug_select_parents(int nf, int nc, int Kc, int ntri, int weighting, int nested, const double* P, const double* Pc, const int* nearest,
+                             const int* sample, const int* cadj_ptr, const int* cadj, const int* tris, const int* tof_ptr, const int* tof,
+                             const int* NBc, int mode, unsigned char* cnt, unsigned char* kind, int* col, double* w) try {
+    if (nf <= 0 || nc <= 0 || Kc <= 0 || ntri < 0 || weighting < 0 || weighting > 2 || mode < 0 || mode > 2) return GMG_ERR_INVALID;
+    if (!P || !Pc || !nearest || !sample || !cadj_ptr || !cadj || !tris || !tof_ptr || !tof || !NBc || !cnt || !kind || !col || !w) return GMG_ERR_INVALID;
+    // every index the selection follows, checked once: the device stage reads without bounds
+    if (cadj_ptr[0] != 0 || tof_ptr[0] != 0) return GMG_ERR_INVALID;
+    for (int c = 0; c < nc; ++c) if (cadj_ptr[c + 1] < cadj_ptr[c] || tof_ptr[c + 1] < tof_ptr[c]) return GMG_ERR_INVALID;
+    for (int f = 0; f < nf; ++f) if (nearest[f] < 0 || nearest[f] >= nc) return GMG_ERR_INVALID;
+    for (int q = 0; q < cadj_ptr[nc]; ++q) if (cadj[q] < 0 || cadj[q] >= nc) return GMG_ERR_INVALID;
+    for (size_t q = 0; q < 3 * (size_t)ntri; ++q) if (tris[q] < 0 || tris[q] >= nc) return GMG_ERR_INVALID;
+    for (size_t q = 0; q < (size_t)nc * Kc; ++q) if (NBc[q] >= nc) return GMG_ERR_INVALID;
+    for (int c = 0; c < nc; ++c)
+        for (int q = tof_ptr[c]; q < tof_ptr[c + 1]; ++q) {        // (the rotation to c only ends when c is a corner)
+            if (tof[q] < 0 || tof[q] >= ntri) return GMG_ERR_INVALID;
+            const int* t = tris + 3 * (size_t)tof[q];
+            if (t[0] != c && t[1] != c && t[2] != c) return GMG_ERR_INVALID;
+        }
+    HierarchyOptions::SelectJob j;
+    j.nf = nf; j.nc = nc; j.Kc = Kc; j.ntri = ntri; j.weighting = weighting; j.nested = nested ? 1 : 0;
+    j.P = P; j.Pc = Pc; j.nearest = nearest; j.sample = sample; j.cadj_ptr = cadj_ptr; j.cadj = cadj; j.tris = tris;
+    j.tof_ptr = tof_ptr; j.tof = tof; j.NBc = NBc; j.cnt = cnt; j.kind = kind; j.col = col; j.w = w;
+    if (mode == 0) { HierarchyBuilder::select_job_on_host(j, false); return GMG_OK; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { (void)hipGetLastError(); return GMG_ERR_NO_DEVICE; }
+    if (!hierarchy_select_on_device(j)) return GMG_ERR_HIP;      // the stage declined: no silent host rows here
+    if (mode == 2) HierarchyBuilder::select_job_on_host(j, true);
     return GMG_OK;
 } GMG_CATCH_0
 

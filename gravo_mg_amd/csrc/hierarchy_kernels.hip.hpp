@@ -42,18 +42,24 @@ struct EdgeMap {                      // the host's SmallIntFloatMap: insertion 
     }
 };
 
+// std::max / std::min as the host code evaluates them -- the first argument unless the comparison says otherwise -- not fmax / fmin: the
+// hardware maximum orders the zeros (max(-0.0, +0.0) = +0.0) where std::max(-0.0, 0.) keeps -0.0, and it drops a NaN where std::max keeps
+// its first argument (tests/test_gpu_select_parents.py: the point on its own cell position).
+__device__ __forceinline__ double host_max(double a, double b) { return a < b ? b : a; }
+__device__ __forceinline__ double host_min(double a, double b) { return b < a ? b : a; }
+
 __device__ __forceinline__ void inv_dist_weights(const double* Pc, D3 p, const int* ids, int cnt, double* w) {
     double s = 0.0;
-    for (int j = 0; j < cnt; ++j) { w[j] = 1.0 / fmax(1e-8, norm(sub(p, load3(Pc, ids[j])))); s += w[j]; }
+    for (int j = 0; j < cnt; ++j) { w[j] = 1.0 / host_max(1e-8, norm(sub(p, load3(Pc, ids[j])))); s += w[j]; }
     for (int j = 0; j < cnt; ++j) w[j] /= s;
 }
 
 __device__ __forceinline__ void edge_weights(int c, int other, D3 p, D3 pc, const double* Pc, int weighting, double& w1, double& w2) {
     if (weighting == 0) {
         const D3 e = sub(load3(Pc, other), pc);
-        const double len = fmax(norm(e), 1e-8);
+        const double len = host_max(norm(e), 1e-8);
         w2 = dot(sub(p, pc), normalized(e)) / len;
-        w2 = fmin(fmax(w2, 0.), 1.);
+        w2 = host_min(host_max(w2, 0.), 1.);
         w1 = 1. - w2;
     } else if (weighting == 1) {
         w1 = w2 = 0.5;

@@ -417,6 +417,42 @@ public:
         return R;
     }
 
+    // Test access (gmg_debug_select_parents): select_point for the points of one job given as flat arrays (the layout a device stage
+    // gets), one record per point in the job's outputs.  Triangle normals are made here the way build() makes them (j.tri_normal is
+    // not read).  only_unhandled: just the points a device stage left at cnt = 255 -- what build() does with its records.  A row
+    // select_point counts under no kind (the nested sample) gets kind 4, the device stage's code for it.
+    static void select_job_on_host(const HierarchyOptions::SelectJob& j, bool only_unhandled) {
+        const detail::View<V3> P(reinterpret_cast<const V3*>(j.P), (size_t)j.nf);
+        const V3* pc = reinterpret_cast<const V3*>(j.Pc);
+        const std::vector<V3> Pc(pc, pc + j.nc);
+        const std::vector<int> nearest(j.nearest, j.nearest + j.nf), sample(j.sample, j.sample + j.nc);
+        const std::vector<int> tof_ptr(j.tof_ptr, j.tof_ptr + j.nc + 1), tof(j.tof, j.tof + j.tof_ptr[j.nc]);
+        const std::vector<int> NBc(j.NBc, j.NBc + (size_t)j.nc * j.Kc);
+        std::vector<std::vector<int>> cadj((size_t)j.nc);
+        for (int c = 0; c < j.nc; ++c) cadj[c].assign(j.cadj + j.cadj_ptr[c], j.cadj + j.cadj_ptr[c + 1]);
+        std::vector<std::array<int, 3>> tris((size_t)j.ntri);
+        std::vector<V3> tri_normal((size_t)j.ntri);
+        for (int t = 0; t < j.ntri; ++t) {
+            tris[t] = {j.tris[3 * (size_t)t], j.tris[3 * (size_t)t + 1], j.tris[3 * (size_t)t + 2]};
+            tri_normal[t] = detail::normalized(detail::cross(Pc[tris[t][1]] - Pc[tris[t][0]], Pc[tris[t][2]] - Pc[tris[t][0]]));
+        }
+        HierarchyOptions opt;
+        opt.weighting = j.weighting; opt.nested = j.nested != 0;
+        parallel_ranges(j.nf, std::max(1, std::min(hw_threads(), 64)), [&](int lo, int hi, int) {
+            detail::SmallIntFloatMap inside_edge;
+            for (int f = lo; f < hi; ++f) {
+                if (only_unhandled && j.cnt[f] != 255) continue;
+                int n = 0;
+                auto emit = [&](int, int c, double w) { j.col[3 * (size_t)f + n] = c; j.w[3 * (size_t)f + n] = w; ++n; };
+                std::array<int, 4> kinds{0, 0, 0, 0};
+                select_point(f, P, Pc, nearest, sample, cadj, tof_ptr, tof, tris, tri_normal, NBc, j.Kc, opt, inside_edge, emit, kinds);
+                j.cnt[f] = (unsigned char)n;
+                j.kind[f] = 4;
+                for (int z = 0; z < 4; ++z) if (kinds[z]) j.kind[f] = (unsigned char)z;
+            }
+        }, 4096);
+    }
+
 private:
     // EL keeps every edge length (slot i*K + j = |P[i] - P[NB[i*K + j]]|): the sampler and the clustering need the same
     // lengths again (56 per sample, one per relaxation) and read them instead of recomputing gathers + square roots.

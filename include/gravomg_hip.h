@@ -352,7 +352,8 @@ typedef struct {
                               FASTDISK sampler -- resetting the samples (csrc/host_hierarchy.hpp::voronoi_dijkstra); 1: run the sweep as written
                               (same hierarchy bit for bit; the cross-check of tests/test_hierarchy_restatement.py) */
     int use_device;        /* 1 (default): with a HIP device the per-point parent selection (multigrid_solver.cpp:291-452) of levels with >= 200 000 points runs
-                              on it -- same prolongations, bit for bit; 0: host only */
+                              on it -- same prolongations, bit for bit; 0: host only; 2 (a test setting): every level runs on the device whatever its
+                              size, so that small inputs reach the device stage (tests/test_gpu_hierarchy.py) -- slower than 1 on small levels */
 } gmg_hierarchy_options;
 
 int gmg_hierarchy_options_default(gmg_hierarchy_options* o);

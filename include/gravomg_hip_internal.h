@@ -23,6 +23,21 @@ int gmg_debug_sell_copy(gmg_handle h, int k, int which, int64_t* slice_ptr, int*
  *                       N < 0: the first -N slices (a prefix, c16 mode 1); 0: off.  Results must not change (tests/test_gpu_setup.py). */
 int gmg_debug_set(gmg_handle h, const char* key, double value);
 
+/* The per-point parent selection of ONE hierarchy level (multigrid_solver.cpp:291-452) on job arrays the caller builds by hand, in the layout of
+ * HierarchyOptions::SelectJob (csrc/host_hierarchy.hpp): P nf x 3, Pc nc x 3, nearest nf, sample nc, cadj_ptr nc + 1 / cadj (sorted neighbour cells),
+ * tris ntri x 3, tof_ptr nc + 1 / tof (triangles of every cell, ascending), NBc nc x Kc (-1 padded).  Out, one record per point: cnt[nf] entries of
+ * the row, kind[nf] (0 triangle, 1 edge, 2 closest three, 3 single / one neighbour, 4 nested sample), col[3 nf], w[3 nf]; entries beyond cnt are
+ * not written.  mode 0: the host routine (HierarchyBuilder::select_point, triangle normals as the builder makes them) for every point;
+ * mode 1: the device stage as the builder calls it (same upload / launch / download code), raw records, cnt = 255 for a point it hands back;
+ * mode 2: what the builder makes of them -- device records, the points at cnt = 255 redone by the host routine.  Modes 1 and 2 return
+ * GMG_ERR_NO_DEVICE / GMG_ERR_HIP when the stage does not run (no host rows instead).  Indices are checked (GMG_ERR_INVALID). */
+int gmg_debug_select_parents(int nf, int nc, int Kc, int ntri, int weighting, int nested, const double* P, const double* Pc, const int* nearest,
+                             const int* sample, const int* cadj_ptr, const int* cadj, const int* tris, const int* tof_ptr, const int* tof,
+                             const int* NBc, int mode, unsigned char* cnt, unsigned char* kind, int* col, double* w);
+/* Rows of U_k by kind, as the builder counted them (host and device levels alike): out[0..3] = containing triangle, edge, closest three,
+ * single / one neighbour.  Lets an end-to-end test say which branches of the selection its input reached. */
+int gmg_hierarchy_debug_row_kinds(gmg_hierarchy hh, int k, int* out);
+
 /* Host-only Galerkin product Ac = U^T A U (CSC in / CSC out, caller sizes the output with the first call:
  * pass colptr_out only to get nnz in colptr_out[n_coarse]).  Exposed for the RAP parity tests. */
 int gmg_host_galerkin(int n, const int* a_colptr, const int* a_rowidx, const double* a_val,

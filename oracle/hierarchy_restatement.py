@@ -1,6 +1,7 @@
 """Pure-Python restatement of the reference's default hierarchy construction -- TEST INFRASTRUCTURE ONLY.
 
-Follows gravomg/src/multigrid_solver.cpp line by line (FASTDISK sampling, BARYCENTRIC weights, check_voronoi, not nested):
+Follows gravomg/src/multigrid_solver.cpp line by line (FASTDISK sampling, BARYCENTRIC weights, check_voronoi, not nested;
+select_point, the per-point parent selection on its own, also with UNIFORM / INVDIST weights and nested):
     constructProlongation :62-469      computeAverageEdgeLength :695-711      fastDiskSample :975-1013
     constructDijkstraWithCluster :1015-1056      inTriangle :471-507      inverseDistanceWeights :515-526
 It shares no code with gravo_mg_amd/csrc/host_hierarchy.hpp (the product's C++ builder) and is only practical for a
@@ -99,8 +100,9 @@ def in_triangle(p, tri, nrm, pos, inside_edge):            # :471-507
     plane = float((p - v1) @ nrm)
     q = p - plane * nrm
     area2 = float(np.cross(v2 - v1, v3 - v1) @ nrm)
-    b0 = float(np.cross(v3 - v2, q - v2) @ nrm) / area2
-    b1 = float(np.cross(v1 - v3, q - v3) @ nrm) / area2
+    with np.errstate(divide="ignore", invalid="ignore"):                 # IEEE division: a zero-area triangle gives NaN / inf, as in C++
+        b0 = float(np.float64(np.cross(v3 - v2, q - v2) @ nrm) / np.float64(area2))
+        b1 = float(np.float64(np.cross(v1 - v3, q - v3) @ nrm) / np.float64(area2))
     b2 = 1.0 - b0 - b1
     if tri[1] not in inside_edge:
         inside_edge[tri[1]] = float(np.float32(_norm(v1p - float(v1p @ e12) * e12)))    # std::map<int, float>
@@ -119,6 +121,71 @@ def inverse_distance_weights(pos, p, ids):                 # :515-526
     w = [1.0 / max(1e-8, _norm(p - pos[i])) for i in ids]
     s = sum(w)
     return [x / s for x in w]
+
+
+def uniform_weights(n):                                    # :509-513
+    return [1.0 / n] * n
+
+
+def edge_weights(Pc, p, c, other, weighting):              # :316-337 and :404-426: two parents, the cell first
+    if weighting == 1:
+        return uniform_weights(2)
+    if weighting == 2:
+        return inverse_distance_weights(Pc, p, [c, other])
+    e = Pc[other] - Pc[c]
+    ln = max(_norm(e), 1e-8)
+    w2 = float((p - Pc[c]) @ _normalized(e)) / ln
+    w2 = min(max(w2, 0.0), 1.0)
+    return [1.0 - w2, w2]
+
+
+def select_point(f, P, Pc, nearest, sample, cadj, tris, normals, tris_of, NBc, weighting=0, nested=False):
+    """Parents and weights of fine point f (:293-453) as (cols, weights), in the order the triplets are pushed.
+    Per-level arrays as build() makes them: cadj[c] the sorted neighbour cells, tris / normals the candidate triangles in stored
+    order with their unit normals, tris_of[c] a cell's triangles ascending, NBc the -1 padded table of the coarse level.
+    weighting: 0 barycentric, 1 uniform, 2 inverse distance (multigrid_solver.h:48-52)."""
+    p = P[f]
+    c = int(nearest[f])
+    if nested and sample[c] == f:                                        # :299-302
+        return [c], [1.0]
+    if len(cadj[c]) == 0:                                                # :304-308
+        return [c], [1.0]
+    if len(cadj[c]) == 1:                                                # :309-338
+        other = int(cadj[c][0])
+        return [c, other], edge_weights(Pc, p, c, other, weighting)
+    inside_edge = {}
+    found = None
+    for t in tris_of[c]:                                                 # :351-366
+        tri = [int(v) for v in tris[t]]
+        while tri[0] != c:
+            tri = tri[1:] + tri[:1]
+        dist, bary = in_triangle(p, tri, normals[t], Pc, inside_edge)
+        if dist >= 0.0:
+            found = (tri, bary)
+            break
+    if found:                                                            # :368-387
+        tri, bary = found
+        if weighting == 1:
+            return tri, uniform_weights(3)
+        if weighting == 2:
+            return tri, inverse_distance_weights(Pc, p, tri)
+        return tri, list(bary)
+    edge_to = None
+    for key in sorted(inside_edge):                                      # std::map iterates in key order; first hit wins (:392-401)
+        if inside_edge[key] >= 0.0:
+            edge_to = key
+            break
+    if edge_to is not None:
+        return [c, edge_to], edge_weights(Pc, p, c, edge_to, weighting)
+    # closest three (:429-448): always inverse distance; with fewer than two candidates the reference reads past its list,
+    # the row is then what there is
+    cand = sorted((_norm(p - Pc[nb]), int(nb)) for nb in NBc[c] if nb >= 0 and nb != c)
+    ids = [c] + [nb for _, nb in cand[:2]]
+    return ids, inverse_distance_weights(Pc, p, ids)
+
+
+def triangle_normal(Pc, tri):                              # :266-269, from the stored vertex order
+    return _normalized(np.cross(Pc[tri[1]] - Pc[tri[0]], Pc[tri[2]] - Pc[tri[0]]))
 
 
 def build(pos, neigh, ratio=8.0, lower_bound=1000):
@@ -187,53 +254,11 @@ def build(pos, neigh, ratio=8.0, lower_bound=1000):
                     if v3 in set(cadj[v2]):
                         t = len(tris)
                         tris.append((c, v2, v3))
-                        normals.append(_normalized(np.cross(Pc[v2] - Pc[c], Pc[v3] - Pc[c])))
+                        normals.append(triangle_normal(Pc, (c, v2, v3)))
                         tris_of[c].append(t); tris_of[v2].append(t); tris_of[v3].append(t)
         rows, cols, vals = [], [], []                                    # :291-452
         for f in range(nf):
-            p = P[f]
-            c = int(nearest[f])
-            pc = Pc[c]
-
-            def edge_row(other):
-                e = Pc[other] - pc
-                ln = max(_norm(e), 1e-8)
-                w2 = float((p - pc) @ _normalized(e)) / ln
-                w2 = min(max(w2, 0.0), 1.0)
-                rows.extend([f, f]); cols.extend([c, other]); vals.extend([1.0 - w2, w2])
-
-            if not cadj[c]:
-                rows.append(f); cols.append(c); vals.append(1.0)
-                continue
-            if len(cadj[c]) == 1:
-                edge_row(cadj[c][0])
-                continue
-            inside_edge = {}
-            found = None
-            for t in tris_of[c]:
-                tri = list(tris[t])
-                while tri[0] != c:
-                    tri = tri[1:] + tri[:1]
-                dist, bary = in_triangle(p, tri, normals[t], Pc, inside_edge)
-                if dist >= 0.0:
-                    found = (tri, bary)
-                    break
-            if found:
-                tri, bary = found
-                for j in range(3):
-                    rows.append(f); cols.append(tri[j]); vals.append(bary[j])
-                continue
-            edge_to = None
-            for key in sorted(inside_edge):                               # std::map iterates in key order; first hit wins
-                if inside_edge[key] >= 0.0:
-                    edge_to = key
-                    break
-            if edge_to is not None:
-                edge_row(edge_to)
-                continue
-            cand = sorted((_norm(p - Pc[nb]), int(nb)) for nb in NBc[c] if nb >= 0 and nb != c)
-            ids = [c] + [nb for _, nb in cand[:2]]
-            w = inverse_distance_weights(Pc, p, ids)
+            ids, w = select_point(f, P, Pc, nearest, sample, cadj, tris, normals, tris_of, NBc)
             for i, wi in zip(ids, w):
                 rows.append(f); cols.append(i); vals.append(wi)
         U = sp.coo_matrix((vals, (rows, cols)), shape=(nf, nc)).tocsc()   # setFromTriplets: duplicates summed
