@@ -54,6 +54,15 @@ class GmgHierarchyOptions(C.Structure):
     ]
 
 
+class GmgDeviceVectors(C.Structure):
+    """gmg_device_vectors: device pointers (plain integers) and strides in elements of rhs, x0 (0 = NULL: the initial guess is rhs) and x."""
+    _fields_ = [
+        ("rhs", C.c_void_p), ("rhs_row_stride", C.c_int64), ("rhs_col_stride", C.c_int64),
+        ("x0", C.c_void_p), ("x0_row_stride", C.c_int64), ("x0_col_stride", C.c_int64),
+        ("x", C.c_void_p), ("x_row_stride", C.c_int64), ("x_col_stride", C.c_int64),
+    ]
+
+
 _ip = C.POINTER(C.c_int)
 _dp = C.POINTER(C.c_double)
 _vp = C.c_void_p
@@ -88,6 +97,8 @@ SIGNATURES = {
     "gmg_smooth_residual": (C.c_int, [_vp, C.c_int, _dp, _dp, C.c_int, C.c_int, C.c_int, _dp]),
     "gmg_solve": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp]),
     "gmg_solve_x0_rhs": (C.c_int, [_vp, _dp, _dp, C.c_int, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp]),
+    "gmg_solve_device": (C.c_int, [_vp, C.POINTER(GmgDeviceVectors), C.c_int, C.c_double, C.c_int, C.c_int, _ip, _dp, _dp]),
+    "gmg_set_system_values_device": (C.c_int, [_vp, C.c_void_p, C.c_int64]),
     "gmg_load_problem": (C.c_int, [_vp, _dp, _dp, C.c_int]),
     "gmg_run_cycles": (C.c_int, [_vp, C.c_int, C.c_int, _dp]),
     "gmg_fetch_solution": (C.c_int, [_vp, _dp]),
@@ -626,6 +637,27 @@ class Engine:
     # -- multi-GPU steps (device pointers / stream handles are plain integers)
     def set_stream(self, stream_handle: int):
         self._chk(lib().gmg_set_stream(self._h, _vp(stream_handle) if stream_handle else None))
+
+    # -- caller-owned device memory (device pointers are plain integers, strides in elements)
+    def solve_device(self, rhs_ptr: int, rhs_strides, x_ptr: int, x_strides, d: int, x0_ptr: int = 0, x0_strides=(0, 0), tol=1e-4, stop_type=2,
+                     max_iter=100):
+        """gmg_solve_device on the engine's current stream (set_stream): rhs, x0 (0: the initial guess is rhs) and x are n x d blocks in device
+        memory, `*_strides` = (row stride, column stride).  Returns (iterations, residue, convergence[(ms, residue), ...]); x holds the last
+        iterate when the call returns."""
+        v = GmgDeviceVectors(int(rhs_ptr) or None, int(rhs_strides[0]), int(rhs_strides[1]), int(x0_ptr) or None, int(x0_strides[0]), int(x0_strides[1]),
+                             int(x_ptr) or None, int(x_strides[0]), int(x_strides[1]))
+        iters, res = C.c_int(), C.c_double()
+        conv = np.zeros(2 * max(int(max_iter), 1))
+        rc = lib().gmg_solve_device(self._h, C.byref(v), int(d), float(tol), int(stop_type), int(max_iter), C.byref(iters), C.byref(res), _pd(conv))
+        self.diverged = rc == DIVERGED
+        if not self.diverged:
+            self._chk(rc)
+        return iters.value, res.value, conv[: 2 * iters.value].reshape(-1, 2)
+
+    def set_system_values_device(self, val_ptr: int, nnz: int):
+        """gmg_set_system_values_device: the values-only refresh of set_system from `nnz` contiguous float64 values in device memory (the live
+        system's pattern, in the storage order of the matrix last given to set_system), ready on the engine's current stream."""
+        self._chk(lib().gmg_set_system_values_device(self._h, int(val_ptr) or None, int(nnz)))
 
     def dist_partition(self, rank: int, world: int):
         """Before use_hierarchy / set_system: lay out and keep only rank `rank`'s rows of levels 0-1 (gmg_dist_partition)."""

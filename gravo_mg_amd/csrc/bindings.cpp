@@ -308,6 +308,10 @@ public:
         if (solver->prepareSystem(mapped.m, &h, &gen) != GMG_OK) { check(); throw std::runtime_error("prepare_system failed"); }
         return std::make_tuple((uintptr_t)h, gen);
     }
+    // device-resident solves (not upstream; gravomg.MultigridSolver.solve_device): the engine that holds the live system (0: none) ...
+    uintptr_t engine_handle() { return (uintptr_t)solver->engineHandle(); }
+    // ... and the word that its system was replaced through the C-ABI: no later solve(lhs, ...) may take `lhs` for the live system
+    void invalidate_system() { solver->systemChangedExternally(); }
     void set_engine_option(const std::string& key, double value) {
         gmg_config& c = solver->engineConfig;
         if (key == "smoother") c.smoother = (int)value;
@@ -380,6 +384,8 @@ PYBIND11_MODULE(gravomg_bindings, m) {
         .def("hierarchy_timing", &MultigridSolver::hierarchy_timing)
         .def("convergence", &MultigridSolver::convergence)
         .def("prepare_system", &MultigridSolver::prepare_system, py::arg("lhs"))
+        .def("engine_handle", &MultigridSolver::engine_handle)
+        .def("invalidate_system", &MultigridSolver::invalidate_system)
         .def("set_engine_option", &MultigridSolver::set_engine_option, py::arg("key"), py::arg("value"))
 #ifdef GMG_TESTING
         .def("_test_report_diverged", &MultigridSolver::test_report_diverged, py::arg("n"))

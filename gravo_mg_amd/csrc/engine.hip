@@ -43,6 +43,7 @@
 #include "host_ldlt.hpp"
 #include "host_plan.hpp"
 #include "host_sparse.hpp"
+#include "device_io_check.hpp"
 #include "kernels.hip.hpp"
 #include "setup_kernels.hip.hpp"
 #include "hierarchy_kernels.hip.hpp"
@@ -674,18 +675,22 @@ int gmg_vcycle(gmg_handle h, const double* b, double* x, int d) try {
     return gmg_fetch_solution(h, x);
 } GMG_CATCH_H
 
-// x0: the initial guess (may be rhs itself: then it is copied on the device, not uploaded); x: receives the last iterate
-static int solve_common(gmg_handle h, const double* rhs, const double* x0, double* x, int d, double tol, int stop_type, int max_iter, int* iters_out,
-                        double* residue_out, double* conv) {
+// The solve loop.  Where the problem comes from and where the last iterate goes is the caller's: load() makes b and x of level 0 resident (and
+// h->loaded_d = d), fetch() delivers x and returns once it is there -- host arrays (gmg_solve, gmg_solve_x0_rhs) or the caller's device memory
+// (gmg_solve_device).  bad_args: what is wrong with the caller's arguments (no device needed to tell), or nullptr.
+extern "C++" {
+template <class Load, class Fetch>
+static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, int stop_type, int max_iter, int* iters_out, double* residue_out, double* conv,
+                        Load&& load, Fetch&& fetch) {
     NEED_DEVICE();
     int rc;
-    if (!rhs || !x0 || !x) return fail(h, GMG_ERR_INVALID, "bad arguments");
+    if (bad_args) return fail(h, GMG_ERR_INVALID, bad_args);
     if ((rc = check_whole_system(h))) return rc;
     if ((rc = check_norm_type(h, stop_type))) return rc;
     if (max_iter < 1) max_iter = 1;      // do { } while: at least one cycle (multigrid_solver.cpp:1411-1417)
     auto t_all = clk::now();
     HelperScope helper_scope(h, d);
-    if ((rc = gmg_load_problem(h, rhs, x0, d))) return rc;
+    if ((rc = load())) return rc;
     h->timing["solve_load"] = ms_since(t_all);
     h->timing["coarse_host_ms"] = 0.0;
     auto t0 = clk::now();
@@ -730,7 +735,7 @@ static int solve_common(gmg_handle h, const double* rhs, const double* x0, doubl
     h->timing["diverged"] = diverged ? 1.0 : 0.0;
     h->timing["blown_up"] = blown ? 1.0 : 0.0;           // stopped early: residue not finite or 1e4 x the smallest seen
     auto t_f = clk::now();
-    if ((rc = gmg_fetch_solution(h, x))) return rc;
+    if ((rc = fetch())) return rc;
     h->timing["solve_fetch"] = ms_since(t_f);
     h->timing["iterations"] = it;
     h->timing["residue"] = residue;
@@ -740,17 +745,89 @@ static int solve_common(gmg_handle h, const double* rhs, const double* x0, doubl
     if (residue_out) *residue_out = residue;
     return diverged ? GMG_DIVERGED : GMG_OK;
 }
+}  // extern "C++"
+
+// x0: the initial guess (may be rhs itself: then it is copied on the device, not uploaded); x: receives the last iterate
+static int solve_host(gmg_handle h, const double* rhs, const double* x0, double* x, int d, double tol, int stop_type, int max_iter, int* iters_out,
+                      double* residue_out, double* conv) {
+    return solve_common(h, rhs && x0 && x ? nullptr : "bad arguments", d, tol, stop_type, max_iter, iters_out, residue_out, conv,
+                        [&] { return gmg_load_problem(h, rhs, x0, d); }, [&] { return gmg_fetch_solution(h, x); });
+}
 
 int gmg_solve(gmg_handle h, const double* rhs, double* x, int d, double tol, int stop_type, int max_iter, int* iters_out,
               double* residue_out, double* conv) try {
-    return solve_common(h, rhs, x, x, d, tol, stop_type, max_iter, iters_out, residue_out, conv);
+    return solve_host(h, rhs, x, x, d, tol, stop_type, max_iter, iters_out, residue_out, conv);
 } GMG_CATCH_H
 
 // The reference's binding always starts from x0 = rhs (gravomg_bindings/src/cpp/core.cpp:69): this entry point says so, and the
 // caller neither fills x with a copy of rhs nor pays for the comparison gmg_solve makes to find that out.  x is output only.
 int gmg_solve_x0_rhs(gmg_handle h, const double* rhs, double* x, int d, double tol, int stop_type, int max_iter, int* iters_out,
                      double* residue_out, double* conv) try {
-    return solve_common(h, rhs, rhs, x, d, tol, stop_type, max_iter, iters_out, residue_out, conv);
+    return solve_host(h, rhs, rhs, x, d, tol, stop_type, max_iter, iters_out, residue_out, conv);
+} GMG_CATCH_H
+
+// The load step on the caller's device memory: what gmg_load_problem leaves behind -- b and x of level 0 in device numbering, padding rows
+// zero, with inner_precision = 1 the defect of the initial guess as the fp32 right-hand side -- from one gather kernel on the handle's stream.
+// Every check comes before the first enqueue.
+static int load_problem_device(gmg_handle h, const gmg_device_vectors& v, int d) {
+    int rc = check_level(h, 0, false);
+    if (rc) return rc;
+    Level& l = h->lv[0];
+    if (const char* why = device_vectors_fault(&v, l.n, d)) return fail(h, GMG_ERR_INVALID, why);      // (the extents, which need n)
+    if ((rc = check_device_vectors(h, v, l.n, d))) return rc;
+    if ((rc = ensure_vectors(h, d))) return rc;
+    launch_permute_in2_strided(h, l, v, d);
+    if (h->cfg.inner_precision && (rc = launch_residual_to_f32(h, d, -1))) return rc;    // defect of the initial guess -> b32
+    h->loaded_d = d;
+    return GMG_OK;
+}
+
+int gmg_solve_device(gmg_handle h, const gmg_device_vectors* v, int d, double tol, int stop_type, int max_iter, int* iters_out,
+                     double* residue_out, double* conv) try {
+    return solve_common(h, device_vectors_fault(v, 1, d), d, tol, stop_type, max_iter, iters_out, residue_out, conv,
+                        [&] { return load_problem_device(h, *v, d); },
+                        [&] {
+                            launch_permute_out_strided(h, h->lv[0], *v, d);
+                            HIPCHK(hipStreamSynchronize(h->stream));
+                            return (int)GMG_OK;
+                        });
+} GMG_CATCH_H
+
+// gmg_set_system's values-only refresh with the values already on the device (include/gravomg_hip.h)
+int gmg_set_system_values_device(gmg_handle h, const double* d_val, int64_t nnz) try {
+    NEED_DEVICE();
+    int rc;
+    if (h->live != LiveSystem::system) return fail(h, GMG_ERR_STATE, h->live == LiveSystem::placeholder ? "no system set: the handle holds the prepared structure only (call gmg_set_system first)" : "no system set (call gmg_set_system first)");
+    if ((rc = check_whole_system(h))) return rc;
+    if (!h->live_key_valid || !h->refill_ready || (int)h->lv.size() != h->L + 1 || !refresh_possible(h) || h->live_from_copy)
+        return fail(h, GMG_ERR_STATE, "the live system cannot be refreshed in place (set up by the host planner, or from arrays that were not in canonical storage): use gmg_set_system");
+    Level& l0 = h->lv[0];
+    if (nnz != l0.nnz) return fail(h, GMG_ERR_STATE, "nnz = " + std::to_string(nnz) + " but the live system stores " + std::to_string(l0.nnz) + " entries");
+    if (!d_val) return fail(h, GMG_ERR_INVALID, "d_val is NULL");
+    if ((rc = check_device_block(h, d_val, nnz - 1, "d_val"))) return rc;
+    auto t_all = clk::now();
+    HIPCHK(hipSetDevice(h->cfg.device));
+    if (l0.ord.blocked && h->cfg.block_from_level >= 1) {
+        // a level 0 that gmg_config::block_fine blocked stays blocked only while the new values pass its sign test (values_only does the same on the host)
+        DevTmp<int> d_bad;
+        if ((rc = d_bad.alloc(h, 1))) return rc;
+        int bad = 0;
+        HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(int), h->stream));
+        hipLaunchKernelGGL(gmgk::stieltjes_signs_flag, dim3((l0.n + 255) / 256), dim3(256), 0, h->stream, l0.n, l0.dA.ptr, l0.dA.idx, d_val, d_bad.p);
+        HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (bad) return fail(h, GMG_ERR_STATE, "these values fail the sign test of the blocked level 0 (gmg_config::block_fine: positive diagonal, no positive off-diagonal entry): this system needs a full set-up through gmg_set_system");
+    }
+    HIPCHK(hipMemcpyAsync(l0.dA.val, d_val, sizeof(double) * (size_t)nnz, hipMemcpyDeviceToDevice, h->stream));
+    rc = refresh_system_values(h, l0.n, nullptr, t_all, /*values_uploaded=*/true);
+    if (rc == GMG_OK) {
+        h->timing["setup_structure_prepared"] = 0.0;
+        h->timing["t_verdict"] = h->timing["setup_total"] = ms_since(t_all);
+        h->timing["upload"] = h->timing["setup_total"] - h->timing["reduction"];
+        return GMG_OK;
+    }
+    lose_live_system(h); h->refill_ready = false;       // half-refreshed values: no solves on them
+    return rc == 1 ? fail(h, GMG_ERR_STATE, "value refresh could not run in place") : rc;
 } GMG_CATCH_H
 
 // ---- multi-GPU: one process per GPU, level 0 row-partitioned per colour, levels >= 1 replicated ---------------

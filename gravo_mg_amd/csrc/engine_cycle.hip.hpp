@@ -646,6 +646,59 @@ int to_host(gmg_handle h, int k, const double* src, int d, double* dst) {
     return GMG_OK;
 }
 
+// ---- caller-owned device memory (gmg_solve_device, gmg_set_system_values_device) ------------------------
+
+// the column count as a template argument where the kernels have a fast path (1 .. 4), 0 = run-time d otherwise
+#define DISPATCH_D_ANY(dc, ...)          \
+    switch (dc) {                        \
+        case 1: { constexpr int D = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int D = 2; __VA_ARGS__; } break; \
+        case 3: { constexpr int D = 3; __VA_ARGS__; } break; \
+        case 4: { constexpr int D = 4; __VA_ARGS__; } break; \
+        default: { constexpr int D = 0; __VA_ARGS__; } break; \
+    }
+
+// `what` [0 .. extent] (doubles) must be device memory of the handle's device, inside one allocation.  Nothing but device memory may reach
+// a kernel: a host pointer would fault the device.
+int check_device_block(gmg_handle h, const void* p, int64_t extent, const char* what) {
+    hipPointerAttribute_t attr;
+    std::memset(&attr, 0, sizeof(attr));
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return fail(h, GMG_ERR_INVALID, std::string(what) + " is not device memory (unknown to the HIP runtime: a host pointer?)"); }
+    if (attr.type != hipMemoryTypeDevice || attr.isManaged) return fail(h, GMG_ERR_INVALID, std::string(what) + " is not plain device memory (host, pinned or managed memory)");
+    if (attr.device != h->cfg.device) return fail(h, GMG_ERR_INVALID, std::string(what) + " lives on device " + std::to_string(attr.device) + ", the handle on device " + std::to_string(h->cfg.device));
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return GMG_OK; }      // (no range to compare with: virtual-memory mappings)
+    const size_t off = (size_t)((const char*)p - (const char*)base);
+    if (off > size || (size_t)(extent + 1) > (size - off) / sizeof(double)) return fail(h, GMG_ERR_INVALID, std::string(what) + " with these strides does not fit the allocation it points into");
+    return GMG_OK;
+}
+
+int check_device_vectors(gmg_handle h, const gmg_device_vectors& v, int n, int d) {
+    int rc;
+    int64_t e = 0;
+    (void)strided_extent(n, d, v.rhs_row_stride, v.rhs_col_stride, &e);           // (shapes were checked: device_vectors_fault)
+    if ((rc = check_device_block(h, v.rhs, e, "rhs"))) return rc;
+    if (v.x0) {
+        (void)strided_extent(n, d, v.x0_row_stride, v.x0_col_stride, &e);
+        if ((rc = check_device_block(h, v.x0, e, "x0"))) return rc;
+    }
+    (void)strided_extent(n, d, v.x_row_stride, v.x_col_stride, &e);
+    return check_device_block(h, v.x, e, "x");
+}
+
+// level-0 b <- rhs and x <- x0 (or rhs) in one pass over the ordering; x <- level-0 iterate
+void launch_permute_in2_strided(gmg_handle h, Level& l, const gmg_device_vectors& v, int d) {
+    const dim3 grid((l.n_pad + 255) / 256);
+    DISPATCH_D_ANY(d, DISPATCH_FLAG(X0, v.x0 != nullptr, hipLaunchKernelGGL((gmgk::permute_in2_strided<D, X0>), grid, dim3(256), 0, h->stream, v.rhs, v.rhs_row_stride,
+                                        v.rhs_col_stride, v.x0, v.x0_row_stride, v.x0_col_stride, l.d_new2old, l.b, l.x, l.n_pad, l.n_pad, d)));
+}
+
+void launch_permute_out_strided(gmg_handle h, Level& l, const gmg_device_vectors& v, int d) {
+    DISPATCH_D_ANY(d, hipLaunchKernelGGL((gmgk::permute_out_strided<D>), dim3((l.n_pad + 255) / 256), dim3(256), 0, h->stream, (const double*)l.x, l.n_pad, l.n_pad,
+                                         l.d_new2old, v.x, v.x_row_stride, v.x_col_stride, d));
+}
+
 // ---- V-cycle legs --------------------------------------------------------------------------------------
 
 // gmg_profile_cycle: an event at every boundary between the legs of a cycle (2 L + 3 of them: before each level's way down, after the

@@ -302,6 +302,8 @@ struct gmg_solver_s {
     std::shared_ptr<DistPlan> plan;       // of the live (or last) partitioned system; reused while the pattern digest and the partition stand
     bool refill_ready = false;        // the live layout was built by the device builders from device-resident A_k: a system with
                                       // the same sparsity pattern only needs its values refreshed
+    bool live_from_copy = false;      // the live system was set up from the engine's canonical copy of the caller's arrays (unsorted / duplicate entries): the
+                                      // resident A_0 is NOT in the caller's storage order (gmg_set_system_values_device refuses)
     bool dist_all_rows = false;
     double *own_x0 = nullptr, *own_b0 = nullptr, *own_r0 = nullptr;   // engine-owned buffers parked while external ones are bound
     bool bound = false;

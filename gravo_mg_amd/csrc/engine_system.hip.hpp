@@ -229,15 +229,22 @@ void stamp_done(gmg_handle h, clk::time_point t_all) {
     h->timing["setup_total"] = ms_since(t_all);                          // wall time of this call (the coarsest factorisation overlaps)
 }
 
+// what refresh_system_values needs of the live levels (it returns 1 without)
+bool refresh_possible(gmg_handle h) {
+    const int L = h->L;
+    for (int k = 0; k <= L; ++k) if (!h->lv[k].dA.ptr || !h->lv[k].dA.idx || !h->lv[k].dA.val) return false;
+    for (int k = 0; k < L; ++k) if (!h->lv[k].d_old2new || !h->lv[k].diag) return false;
+    return h->lv[L].hostA_pattern;
+}
+
 // gmg_set_system for a matrix with the sparsity pattern of the live system: values only.  Returns 1 when it cannot be
 // done in place (nothing has been changed then, except values that the full path overwrites anyway).
-// values_uploaded: the caller has already put `val` into the resident A_0 (the speculative upload of enter_system)
+// values_uploaded: the caller has already put `val` into the resident A_0 (the speculative upload of enter_system; the device copy of
+// gmg_set_system_values_device, which passes val = nullptr)
 // l1_rows_done: ... and has queued the numeric Galerkin pass of the first l1_rows_done rows of level 1 behind it (flag: h->d_aux_err)
 int refresh_system_values(gmg_handle h, int n, const double* val, clk::time_point t_all, bool values_uploaded = false, int l1_rows_done = 0, int l2_rows_done = 0) {
     const int L = h->L;
-    for (int k = 0; k <= L; ++k) if (!h->lv[k].dA.ptr || !h->lv[k].dA.idx || !h->lv[k].dA.val) return 1;
-    for (int k = 0; k < L; ++k) if (!h->lv[k].d_old2new || !h->lv[k].diag) return 1;
-    if (!h->lv[L].hostA_pattern) return 1;
+    if (!refresh_possible(h)) return 1;
     for (auto it = h->timing.begin(); it != h->timing.end();) it = it->first.rfind("t_", 0) == 0 ? h->timing.erase(it) : std::next(it);
     mark_at(h, t_all, "pattern_key");
     int rc;
@@ -915,7 +922,7 @@ int set_system_impl(gmg_handle h, int n, const int* colptr, const int* rowidx, c
     int rc = enter_system(h, n, colptr, rowidx, val, t_all, e);
     if (rc != GMG_OK) return rc;
     const bool live = h->live != LiveSystem::none;
-    if ((rc = values_only(h, n, e, t_all)) != 1) return rc;
+    if ((rc = values_only(h, n, e, t_all)) != 1) { if (rc == GMG_OK) h->live_from_copy = false; return rc; }
     // (the resident values were overwritten ahead of the verdict and the pattern turned out to be another one: the live system is gone -- the
     // full set-up drops it anyway; a failure on the way must not leave a system that solves with foreign values)
     if (e.speculative) {
@@ -930,6 +937,7 @@ int set_system_impl(gmg_handle h, int n, const int* colptr, const int* rowidx, c
     if ((rc = s.run()) || (rc = finish_system(h, n, s.ms_factor, s.inverse_built || placeholder, true, placeholder)) || (rc = s.commit())) return rc;
     stamp_done(h, t_all);
     h->timing["setup_structure_prepared"] = 0.0;
+    h->live_from_copy = e.colptr != colptr;
     return GMG_OK;
 }
 

@@ -1754,6 +1754,77 @@ __global__ void permute_out(const double* __restrict__ src, int ld, int n_pad, c
     for (int c = 0; c < D; ++c) dst[old + (int64_t)c * n] = src[r + (int64_t)c * ld];
 }
 
+// The same two permutations on CALLER-OWNED device memory (gmg_solve_device): element (i, c) of a caller's n x d block sits at
+// ptr[i * row_stride + c * col_stride], strides in elements and 64 bits wide (row_stride * n can pass 2^31).  One thread per device row: the
+// 64 lanes of a wave write 64 consecutive doubles of each column of the level vectors (one 512-byte store per column); their reads follow
+// new2old, which keeps neighbouring rows of a colour class / block close in the caller's numbering.  D = 1 .. 4: the column count at compile
+// time -- every load of a row is issued before the first store; D = 0: `d` columns at run time, any d >= 1.
+//
+// permute_in2_strided: ONE pass over new2old fills both level vectors -- b = rhs and x = x0, or x = rhs when X0 is false (the reference's
+// binding: x0 = rhs; the value is read once and written twice); padding rows get 0.  rhs / x0 carry no __restrict__: they may be one buffer.
+template <int D, bool X0>
+__global__ __launch_bounds__(256) void permute_in2_strided(const double* rhs, int64_t rhs_rs, int64_t rhs_cs, const double* x0, int64_t x0_rs, int64_t x0_cs,
+                                                           const int* __restrict__ new2old, double* __restrict__ b, double* __restrict__ x, int ld,
+                                                           int n_pad, int d) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_pad) return;
+    const int old = new2old[r];
+    const double* pb = rhs + (int64_t)(old >= 0 ? old : 0) * rhs_rs;
+    const double* px = X0 ? x0 + (int64_t)(old >= 0 ? old : 0) * x0_rs : nullptr;
+    if (D > 0) {
+        double vb[D > 0 ? D : 1], vx[D > 0 ? D : 1];
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            vb[c] = old >= 0 ? pb[(int64_t)c * rhs_cs] : 0.0;
+            vx[c] = X0 ? (old >= 0 ? px[(int64_t)c * x0_cs] : 0.0) : vb[c];
+        }
+#pragma unroll
+        for (int c = 0; c < D; ++c) { b[r + (int64_t)c * ld] = vb[c]; x[r + (int64_t)c * ld] = vx[c]; }
+    } else {
+        for (int c = 0; c < d; ++c) {
+            const double vb = old >= 0 ? pb[(int64_t)c * rhs_cs] : 0.0;
+            const double vx = X0 ? (old >= 0 ? px[(int64_t)c * x0_cs] : 0.0) : vb;
+            b[r + (int64_t)c * ld] = vb;
+            x[r + (int64_t)c * ld] = vx;
+        }
+    }
+}
+
+// permute_out_strided: the scatter of the level-0 iterate into the caller's block (padding rows write nothing)
+template <int D>
+__global__ __launch_bounds__(256) void permute_out_strided(const double* __restrict__ src, int ld, int n_pad, const int* __restrict__ new2old,
+                                                           double* __restrict__ dst, int64_t dst_rs, int64_t dst_cs, int d) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_pad) return;
+    const int old = new2old[r];
+    if (old < 0) return;
+    double* p = dst + (int64_t)old * dst_rs;
+    if (D > 0) {
+        double v[D > 0 ? D : 1];
+#pragma unroll
+        for (int c = 0; c < D; ++c) v[c] = src[r + (int64_t)c * ld];
+#pragma unroll
+        for (int c = 0; c < D; ++c) p[(int64_t)c * dst_cs] = v[c];
+    } else {
+        for (int c = 0; c < d; ++c) p[(int64_t)c * dst_cs] = src[r + (int64_t)c * ld];
+    }
+}
+
+// The sign test of gmg_config::block_fine (engine_setup.hip.hpp::stieltjes_signs) on device-resident values: *flag becomes 1 when an outer vector of
+// the compressed pattern (ptr, idx) has no positive diagonal entry or holds a positive off-diagonal one.  One thread per outer vector.
+__global__ __launch_bounds__(256) void stieltjes_signs_flag(int n, const int* __restrict__ ptr, const int* __restrict__ idx, const double* __restrict__ val,
+                                                            int* __restrict__ flag) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n) return;
+    bool diag = false, bad = false;
+    for (int p = ptr[j]; p < ptr[j + 1]; ++p) {
+        const double v = val[p];
+        if (idx[p] == j) { diag = v > 0.0; bad = bad || !diag; }
+        else if (v > 0.0) bad = true;
+    }
+    if (bad || !diag) atomicOr(flag, 1);
+}
+
 // Lumped mass and its inverse in device numbering (weights of the M / M^-1 residual norms); padding rows get 1.
 __global__ void permute_mass(const double* __restrict__ mass, const int* __restrict__ new2old, int n_pad, double* __restrict__ m,
                              double* __restrict__ minv) {

@@ -150,6 +150,11 @@ public:
        C-ABI handle (owned by this object) and a counter that changes whenever the device layout was rebuilt, so that a caller can
        drive the engine-driven multi-GPU cycle (gmg_p2p_*, include/gravomg_hip.h) on it.  Returns a gmg status. */
     int prepareSystem(const SparseMatrix& LHS, gmg_handle* handle, long* generation);
+    /* Device-resident solves (not in the reference; gravomg.MultigridSolver.solve_device): the handle of the engine in use (nullptr before the
+       first engine exists; whether it holds a system is the engine's to say), and the caller's word that it replaced that engine's system behind this object's back (gmg_set_system_values_device) --
+       the next solve() / prepareSystem() then sets its LHS up again whatever its digest, and the generation changes. */
+    gmg_handle engineHandle() const { return engine_; }
+    void systemChangedExternally() { systemReady_ = false; ++systemGeneration_; }
 #ifdef GMG_TESTING
     int testReportDiverged = 0;      // test build of the pybind module only (tests/_native/): the next N default-engine solves report GMG_DIVERGED
 #endif

@@ -114,6 +114,9 @@ class MultigridSolver(object):
 
         self._solve_args = (float(tolerance), int(stopping_criteria), int(max_iter))
         self._dist = None
+        self._n = int(pos.shape[0])
+        self._device = 0                                  # HIP device of the engine (set_engine_option("device", ...))
+        self.device_info = None                           # solve_device(): iterations, residue, diverged of the last call
 
     def solve(self, lhs, rhs):
         """x with lhs @ x = rhs to the tolerance given at construction, V-cycles from the initial guess x0 = rhs
@@ -122,6 +125,87 @@ class MultigridSolver(object):
         if self._dist is not None:
             return self._solve_distributed(_sparse(lhs, "lhs"), _points(rhs, "rhs"))
         return self.solver.solve(_sparse(lhs, "lhs"), _points(rhs, "rhs"))
+
+    # ---- device-resident solves (not upstream) ------------------------------------------------------------------------------------------
+    def solve_device(self, lhs, rhs, x0=None):
+        """solve() for data that lives on the GPU: `rhs` (and `x0`, default: rhs, as in solve()) are float64 CUDA torch tensors of shape (n,) or
+        (n, d) with any strides, the result is a new (n, d) CUDA tensor on rhs.device -- no vector crosses the host link, and the V-cycles are
+        those of solve() bit for bit (gmg_solve_device, include/gravomg_hip.h).  The work is enqueued on torch's CURRENT stream of that device,
+        behind whatever produced rhs there; the call returns when x is complete.
+
+        lhs: a scipy sparse matrix (set up as solve() does); or a 1-D float64 CUDA tensor with the values of a matrix that has the live
+        system's sparsity pattern, in the order of the `.data` of the CSC / CSR matrix last passed as lhs -- refreshed on the device
+        (gmg_set_system_values_device), e.g. `m_val + tau * s_val` of a time-stepping loop; or None: keep the live system.
+
+        TypeError for tensors that are not float64 CUDA tensors on the engine's device, ValueError for shapes; RuntimeError when the engine
+        refuses (no live system for a values tensor, a distributed object, ...) and when the iteration blew up.  Iterations, residue and whether
+        the iteration failed to contract are left in `self.device_info` (solve_device does not retry with another smoother as solve() does)."""
+        import torch                                      # only here: `import gravomg` works without torch
+
+        def tensor(t, what, ndims):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise TypeError(f"{what} must be a CUDA torch tensor (got {'a CPU tensor' if isinstance(t, torch.Tensor) else type(t).__name__})")
+            if t.dtype != torch.float64:
+                raise TypeError(f"{what} must be a float64 tensor (got {t.dtype})")
+            if t.device.index != self._device:
+                raise TypeError(f"{what} is on {t.device}, the engine on HIP device {self._device}")
+            if t.dim() not in ndims:
+                raise ValueError(f"{what} must have {' or '.join(str(k) for k in ndims)} dimension(s)")
+            return t
+
+        if self._dist is not None:
+            raise RuntimeError("solve_device() runs on one GPU; this object was made distributed (enable_distributed)")
+        rhs = tensor(rhs, "rhs", (1, 2))
+        b = rhs[:, None] if rhs.dim() == 1 else rhs
+        if b.shape[0] != self._n or b.shape[1] < 1:
+            raise ValueError(f"rhs must have {self._n} rows and at least one column (got {tuple(rhs.shape)})")
+        g = None
+        if x0 is not None:
+            x0 = tensor(x0, "x0", (1, 2))
+            g = x0[:, None] if x0.dim() == 1 else x0
+            if g.shape != b.shape:
+                raise ValueError(f"x0 must have the shape of rhs (got {tuple(x0.shape)})")
+        values = None
+        if lhs is not None and not sp.issparse(lhs):
+            if not isinstance(lhs, torch.Tensor):
+                raise TypeError("lhs must be a scipy sparse matrix, a CUDA torch tensor of values or None")
+            values = tensor(lhs, "lhs", (1,)).contiguous()
+        import os
+        import sys
+        root = os.path.dirname(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+        if root not in sys.path:
+            sys.path.insert(0, root)
+        from gravo_mg_amd import cabi                     # ctypes view of the same libgravomg_hip.so
+        if sp.issparse(lhs):
+            handle, _ = self.solver.prepare_system(lhs)
+        else:
+            handle = self.solver.engine_handle()
+            if not handle:
+                raise RuntimeError("no live system: the first solve_device() / solve() needs a scipy sparse lhs")
+        eng = cabi.Engine.borrow(handle)
+        tol, stop_type, max_iter = self._solve_args
+        x = torch.empty(b.shape, dtype=torch.float64, device=b.device)
+        stream = torch.cuda.current_stream(b.device)
+        if stream.cuda_stream == 0:
+            stream.synchronize()                          # (the default stream has no handle to give: the engine runs on its own stream, behind it)
+        eng.set_stream(stream.cuda_stream)
+        try:
+            if values is not None:
+                try:
+                    eng.set_system_values_device(values.data_ptr(), values.numel())
+                finally:
+                    self.solver.invalidate_system()       # whatever became of it: the mirror's record of "the live system" no longer holds
+            it, residue, _ = eng.solve_device(b.data_ptr(), b.stride(), x.data_ptr(), x.stride(), b.shape[1],
+                                              x0_ptr=0 if g is None else g.data_ptr(), x0_strides=(0, 0) if g is None else g.stride(),
+                                              tol=tol, stop_type=stop_type, max_iter=max_iter)
+            diverged = bool(eng.diverged)
+            blown = bool(eng.timing("blown_up"))
+        finally:
+            eng.set_stream(0)
+        self.device_info = {"iterations": it, "residue": residue, "diverged": diverged}
+        if not np.isfinite(residue) or blown:
+            raise RuntimeError(f"the V-cycle iteration diverged (residue {residue})")
+        return x
 
     # ---- one process per GPU (not upstream) -------------------------------------------------------------------------------------------
     def enable_distributed(self, rank, world, all_gather, device=None, shard_levels=2, partition_setup=True, exchange="mailbox"):
@@ -217,6 +301,8 @@ class MultigridSolver(object):
         """MI355X engine knobs (not upstream): smoother (0 multicolour Gauss-Seidel, 1 weighted Jacobi), gs_omega, jacobi_omega,
         coarse_mode (0 host LDL^T back-substitution per cycle, 1 dense inverse built and applied on the device, 2 = default: 1 while the coarsest level has <= 8 192 unknowns -- a system solved ONCE is faster with 0), use_graph, block_rows, block_from_level, device."""
         self.solver.set_engine_option(str(key), float(value))
+        if str(key) == "device":
+            self._device = int(value)
 
 
 def _bind(name, args, kwargs):

@@ -177,6 +177,19 @@ int gmg_set_mass(gmg_handle h, int n, const double* mass_diag);
  * still being inspected, so the previous system does not survive a rejected call; the next solve returns GMG_ERR_STATE until a gmg_set_system
  * succeeds (the reference has no persistent system either: solve() receives the LHS every time, multigrid_solver.cpp:1367). */
 int gmg_set_system(gmg_handle h, int n, const int* colptr, const int* rowidx, const double* val);
+/* The values-only refresh of gmg_set_system (the part of multigrid_solver.cpp:1387-1401 that depends on the values: numeric Galerkin passes,
+ * layout refill, numeric LDL^T) from DEVICE memory: d_val holds the nnz values of a matrix with the LIVE system's sparsity pattern, in the
+ * storage order of the arrays last given to gmg_set_system, contiguous, on the handle's device and ready on the handle's stream
+ * (gmg_set_stream).  They are copied device to device over the resident A_0; the result is that of gmg_set_system with the same values
+ * (timing key "setup_values_only" = 1, the same keys otherwise; no host upload).
+ * GMG_ERR_STATE with the handle UNTOUCHED (the old system stays usable): no live system (none set, or only the prepared structure of
+ * gmg_finalize_hierarchy), a partitioned handle, nnz other than the live system's, a live system that cannot be refreshed in place (set up
+ * by the host planner, or from arrays the engine had to bring into canonical storage first), and -- on a level 0 that gmg_config::block_fine
+ * blocked -- values that fail its sign test (positive diagonal, no positive off-diagonal entry: tested by a device kernel over the resident
+ * pattern and d_val, one flag read back BEFORE the copy): such a system needs a full set-up through gmg_set_system.  GMG_ERR_INVALID for a
+ * d_val that is not device memory of the handle's device.  A refresh that fails half-way (GMG_ERR_NUMERIC: zero diagonal, singular
+ * coarsest operator; GMG_ERR_HIP) leaves the handle WITHOUT a system, exactly like gmg_set_system. */
+int gmg_set_system_values_device(gmg_handle h, const double* d_val, int64_t nnz);
 
 /* ---- introspection -------------------------------------------------------------------------- */
 int gmg_num_levels(gmg_handle h);                       /* L, or < 0 */
@@ -236,6 +249,25 @@ int gmg_solve(gmg_handle h, const double* rhs, double* x, int d, double tol, int
 /* The same with the initial guess x0 = rhs, the only one the reference's Python binding ever passes (core.cpp:69): x is OUTPUT only --
  * the caller does not fill it with a copy of rhs, and the engine copies rhs to x on the device instead of comparing and uploading. */
 int gmg_solve_x0_rhs(gmg_handle h, const double* rhs, double* x, int d, double tol, int stop_type, int max_iter,
+                     int* iters_out, double* residue_out, double* conv);
+/* The same loop (multigrid_solver.cpp:1408-1419) on CALLER-OWNED DEVICE memory in natural numbering: nothing crosses the host link.  Element
+ * (i, c) of a block is at ptr[i * row_stride + c * col_stride]; strides are in ELEMENTS, non-negative, 64 bits wide. */
+typedef struct {
+    const double* rhs;  int64_t rhs_row_stride, rhs_col_stride;   /* (d,1) = torch-contiguous n x d, (1,n) = column-major */
+    const double* x0;   int64_t x0_row_stride,  x0_col_stride;    /* x0 == NULL: initial guess = rhs (what the reference's binding always passes, core.cpp:69) */
+    double*       x;    int64_t x_row_stride,   x_col_stride;     /* receives the last iterate, as gmg_solve does */
+} gmg_device_vectors;
+/* One gather kernel fills the level-0 right-hand side and iterate from rhs / x0 (csrc/kernels.hip.hpp::permute_in2_strided), the loop of gmg_solve
+ * runs unchanged, one scatter kernel writes x (permute_out_strided): same iterates, same return values (GMG_DIVERGED included), same timing
+ * keys as gmg_solve on the same data.  Everything runs on the handle's CURRENT stream (gmg_set_stream: e.g. torch's current stream, which
+ * orders the solve behind the kernels that produced rhs); the call returns after that stream has drained, like gmg_run_cycles.
+ * Checked before anything is enqueued: v, rhs or x NULL, d <= 0, a row stride of zero, a negative stride, a column stride of zero for x with
+ * d > 1 -> GMG_ERR_INVALID; so is every pointer that is not device memory of the handle's device (hipPointerGetAttributes: host, pinned and
+ * managed memory and other devices' memory are refused) or whose block does not fit the allocation it points into.  A partitioned handle
+ * (gmg_dist_partition) -> GMG_ERR_STATE.
+ * x may BE rhs or x0 (the same pointer with the same strides): the gather has completed before the scatter starts.  Any other overlap of x
+ * with rhs or x0, or of x with itself, is the caller's error and gives undefined values (never an access outside the blocks). */
+int gmg_solve_device(gmg_handle h, const gmg_device_vectors* v, int d, double tol, int stop_type, int max_iter,
                      int* iters_out, double* residue_out, double* conv);
 
 /* ---- resident problem (device-resident b / x; what gmg_solve and bench.py are built from) ---------- */
