@@ -123,7 +123,7 @@ struct Level {
     // blocked levels (block-hybrid Gauss-Seidel): in-block part (16-bit local columns) + off-block part
     DevSell Ain, Aout;
     unsigned short* ain_col16 = nullptr;
-    // big blocked levels: block-CSR storage instead of the two padded SELL operators (kernels.hip.hpp::gs_blockcsr)
+    // big blocked levels: block-CSR storage instead of the two padded SELL operators (kernels.hip.hpp::gs_block_csrout)
     bool use_bcsr = false;
     int *bc_ptr = nullptr, *bc_mid = nullptr, *bc_col = nullptr;
     double* bc_val = nullptr;

@@ -190,6 +190,37 @@ __device__ __forceinline__ void quad_reduce(T (&acc)[D]) {
     }
 }
 
+// ---- steps that sibling kernels share: one copy each, so that "the same arithmetic" holds by construction ---------------------------
+// The Gauss-Seidel value of a row, x_i^GS = (b_i - sum_{j != i} a_ij x_j) / a_ii, and its relaxation x_i + omega (x_i^GS - x_i).  Two functions,
+// not a flag: the plain form takes no x_i, so a kernel that calls it alone loads none.
+template <class T> __device__ __forceinline__ T gs_row(T bi, T acc, T dg) { return (bi - acc) / dg; }
+template <class T> __device__ __forceinline__ T gs_row(T bi, T acc, T dg, T omega, T xi) { return xi + omega * (gs_row(bi, acc, dg) - xi); }
+
+// (A x)_i from row_dot's off-diagonal sum.  Every residual is this minus b_i (the norm sums) or b_i minus this (spmv_full<MODE 1>,
+// gs_color_residual, the fp32 right-hand side of residual_norm_slices<MODE 1>): the kernels that replace a pass of another agree with it bit for bit.
+template <class T> __device__ __forceinline__ T row_ax(T acc, T dg, T xi) { return acc + dg * xi; }
+__device__ __forceinline__ double norm_term(double v, double w) { return (v * w) * v; }      // a row's term of the check's sums, w v^2 (v = r_i or b_i)
+// The 2 D sums of the NW waves of a block -> partials[slot][2 D]: shuffle tree inside the wave, then the wave sums in index order.  All threads of the
+// block call it (one barrier); `red` is the caller's LDS; SLOT is the type the caller has the slot in (unsigned blockIdx.x or int: widened here, as before).
+// (residual_norm_partials keeps a copy of these lines: with the call, two of its four instantiations were scheduled differently.)
+template <int NW, int D, class SLOT>
+__device__ __forceinline__ void block_sums_store(const double (&sums)[2 * D], double (&red)[NW][2 * D], int wave, int lane, SLOT slot, double* __restrict__ partials) {
+#pragma unroll
+    for (int c = 0; c < 2 * D; ++c) {
+        double v = sums[c];
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) red[wave][c] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * D) {
+        double v = 0.0;
+#pragma unroll
+        for (int w2 = 0; w2 < NW; ++w2) v += red[w2][threadIdx.x];
+        partials[(int64_t)slot * (2 * D) + threadIdx.x] = v;
+    }
+}
+
 // One colour of a multicolour Gauss-Seidel sweep: rows [slice_begin*64, slice_end*64).
 //   x_i <- (b_i - sum_{j != i} a_ij x_j) / a_ii          (gravomg/src/multigrid_solver.cpp:1200-1208)
 // Rows of one colour do not couple, so the parallel update equals the reference's sequential sweep in
@@ -219,18 +250,18 @@ __global__ __launch_bounds__(kBlock) void gs_color(const int64_t* __restrict__ s
 #pragma unroll
         for (int c = 0; c < D; ++c) {
             const T xi = x[row + (int64_t)c * ld];
-            x[row + (int64_t)c * ld] = xi + om * ((b[row + (int64_t)c * ld] - acc[c]) / dg - xi);
+            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, om, xi);
         }
         return;
     }
     if (omega == (T)1.0) {                 // kernel argument: a scalar branch.  The reference's update, no read of x_i
 #pragma unroll
-        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = (b[row + (int64_t)c * ld] - acc[c]) / dg;
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg);
     } else {                               // successive over-relaxation: x_i <- x_i + omega (x_i^GS - x_i)
 #pragma unroll
         for (int c = 0; c < D; ++c) {
             const T xi = x[row + (int64_t)c * ld];
-            x[row + (int64_t)c * ld] = xi + omega * ((b[row + (int64_t)c * ld] - acc[c]) / dg - xi);
+            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
         }
     }
 }
@@ -238,7 +269,7 @@ __global__ __launch_bounds__(kBlock) void gs_color(const int64_t* __restrict__ s
 // The LAST colour launch of a V-cycle's post-smoothing, when a residual check follows: the same update, plus this colour's share of
 // the check's sums.  Right after its update a row's residual needs no second pass over the matrix: the off-diagonal sum is in
 // registers and no later launch changes x before the check, so r_i = sum_{j != i} a_ij x_j + a_ii x_i^new - b_i is exactly the value
-// (same expression, same operands) the norm kernel would compute -- which then only visits the rows of the other colours (a quarter
+// (row_ax and norm_term, same operands) the norm kernel would compute -- which then only visits the rows of the other colours (a quarter
 // less of its 336 MB at four colours).  (The algebraic shortcut r_i = a_ii (1 - omega)(x_i^GS - x_i^old) is NOT used: near the
 // attainable accuracy it under-reports the residue, 5.9e-8 for a true 6.2e-8 on a 7 680-vertex Poisson problem.)  partials[blockIdx][2 D] = sum w r^2 / sum w b^2 over the block's rows (zeros for blocks
 // beyond the range), added by reduce_partials after the norm kernel's own.
@@ -264,31 +295,18 @@ __global__ __launch_bounds__(kBlock) void gs_color_norm(const int64_t* __restric
         for (int c = 0; c < D; ++c) {
             const double bi = b[row + (int64_t)c * ld];
             const double xi = x[row + (int64_t)c * ld];
-            const double xn = omega == 1.0 ? (bi - acc[c]) / dg : xi + omega * ((bi - acc[c]) / dg - xi);
+            const double xn = omega == 1.0 ? gs_row(bi, acc[c], dg) : gs_row(bi, acc[c], dg, omega, xi);
             x[row + (int64_t)c * ld] = xn;
-            const double r = acc[c] + dg * xn - bi;                  // the expression of residual_norm_slices, on the same operands
-            sums[2 * c] = (r * w) * r;
-            sums[2 * c + 1] = (bi * w) * bi;
+            const double r = row_ax(acc[c], dg, xn) - bi;            // residual_norm_slices' own functions, on the same operands
+            sums[2 * c] = norm_term(r, w);
+            sums[2 * c + 1] = norm_term(bi, w);
         }
     }
-#pragma unroll
-    for (int c = 0; c < 2 * D; ++c) {
-        double v = sums[c];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) red[wave][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * D) {
-        double v = 0.0;
-#pragma unroll
-        for (int w2 = 0; w2 < kWavesPerBlock; ++w2) v += red[w2][threadIdx.x];
-        partials[(int64_t)blockIdx.x * (2 * D) + threadIdx.x] = v;
-    }
+    block_sums_store<kWavesPerBlock, D>(sums, red, wave, lane, (unsigned)blockIdx.x, partials);
 }
 
 // The LAST colour launch of the pre-smoothing: the same update, plus the residual r_i = b_i - (sum_{j != i} a_ij x_j + a_ii x_i^new) of
-// its own rows -- the expression of spmv_full<MODE 1> on the same operands (no later launch changes x before the residual), so the
+// its own rows -- b_i - row_ax(..) as in spmv_full<MODE 1>, on the same operands (no later launch changes x before the residual), so the
 // residual kernel only visits the rows of the other colours.
 template <int D, int C16 = 0, int YI = 0>
 __global__ __launch_bounds__(kBlock) void gs_color_residual(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
@@ -307,10 +325,10 @@ __global__ __launch_bounds__(kBlock) void gs_color_residual(const int64_t* __res
     for (int c = 0; c < D; ++c) {
         const double bi = b[row + (int64_t)c * ld];
         double xn;
-        if (omega == 1.0) xn = (bi - acc[c]) / dg;
-        else { const double xi = x[row + (int64_t)c * ld]; xn = xi + omega * ((bi - acc[c]) / dg - xi); }
+        if (omega == 1.0) xn = gs_row(bi, acc[c], dg);
+        else { const double xi = x[row + (int64_t)c * ld]; xn = gs_row(bi, acc[c], dg, omega, xi); }
         x[row + (int64_t)c * ld] = xn;
-        const double ax = acc[c] + dg * xn;
+        const double ax = row_ax(acc[c], dg, xn);
         r[YI ? (int64_t)row * D + c : row + (int64_t)c * ld] = bi - ax;           // (YI: the residual as an interleaved multi-vector, what the restriction gathers from)
     }
 }
@@ -596,6 +614,24 @@ template <class T> inline size_t ep_lds_bytes(int D, int cap_e, int cap_l) {
     return (size_t)D * 64 * sizeof(T) + kEpZeroBytes + stage;
 }
 
+// The reduction of the entry-parallel kernels (gs_block_ep, residual_delta_ep): a row sums its run [eb, ee) of the block's products in stored
+// order, eight reads in flight; reads beyond the run hit the zero slots.  The trip count is the longest run of the wave.
+template <class T>
+__device__ __forceinline__ T ep_run_sum(const T* pbuf, const T* zeroT, int eb, int ee) {
+    T acc = (T)0.0;
+    const T* pa = pbuf + eb;
+    int rem = ee - eb;
+    while (__builtin_amdgcn_ballot_w64(rem > 0)) {
+        T p[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) p[j] = (rem > j ? pa : zeroT)[j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) acc += p[j];
+        pa += 8; rem -= 8;
+    }
+    return acc;
+}
+
 // The sequential half of the entry-parallel block sweep (gs_block_ep below; also the tail of gmgk::restrict_sweep0): the lower in-block entries go
 // through LDS into the row's lane, then the colours of the block one after the other on the block's x in LDS, then the store.  `rhs` = b minus
 // the explicit part.  One wave = one block; every __syncthreads() here is reached by exactly the waves of the workgroup that are still alive
@@ -776,19 +812,7 @@ __global__ __launch_bounds__(64) void gs_block_ep(const int* __restrict__ blk_be
                 for (int e = 64 * kEpE + lane; e < nE; e += 64) pbuf[e] = e_val[e0 + e] * xc[e_col[e0 + e]];
             }
             __syncthreads();
-            // every row sums its run in stored order, eight reads in flight; reads beyond the run hit the zero slots
-            T acc = (T)0.0;
-            const T* pa = pbuf + eb;
-            int rem = ee - eb;
-            while (__builtin_amdgcn_ballot_w64(rem > 0)) {
-                T p[8];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) p[j] = (rem > j ? pa : zeroT)[j];
-#pragma unroll
-                for (int j = 0; j < 8; ++j) acc += p[j];
-                pa += 8; rem -= 8;
-            }
-            rhs[c] -= acc;
+            rhs[c] -= ep_run_sum<T>(pbuf, zeroT, eb, ee);
             __syncthreads();                                           // the buffer is free again
         }
     }
@@ -928,18 +952,7 @@ __global__ __launch_bounds__(64) void residual_delta_ep(const int* __restrict__ 
                 for (int e = 64 * kEpE + lane; e < nE; e += 64) pbuf[e] = -(e_val[e0 + e] * xn[e_col[e0 + e]]);
         }
         __syncthreads();
-        T acc = (T)0.0;
-        const T* pa = pbuf + eb;
-        int rem = ee - eb;
-        while (__builtin_amdgcn_ballot_w64(rem > 0)) {
-            T p[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) p[j] = (rem > j ? pa : zeroT)[j];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) acc += p[j];
-            pa += 8; rem -= 8;
-        }
-        r[row + (int64_t)c * ld] = acc;
+        r[row + (int64_t)c * ld] = ep_run_sum<T>(pbuf, zeroT, eb, ee);
         __syncthreads();
     }
 }
@@ -1094,7 +1107,7 @@ __global__ __launch_bounds__(kBlock) void jacobi_sweep(const int64_t* __restrict
 #pragma unroll
     for (int c = 0; c < D; ++c) {
         const T xi = x_in[row + (int64_t)c * ld];
-        x_out[row + (int64_t)c * ld] = xi + omega * ((b[row + (int64_t)c * ld] - acc[c]) / dg - xi);
+        x_out[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
     }
 }
 
@@ -1112,7 +1125,7 @@ __device__ __forceinline__ void spmv_full_slice(const int64_t* __restrict__ slic
     const T dg = diag[row];
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        const T ax = acc[c] + dg * x[row + (int64_t)c * ld];
+        const T ax = row_ax(acc[c], dg, x[row + (int64_t)c * ld]);
         y[YI ? (int64_t)row * D + c : row + (int64_t)c * ld] = MODE == 1 ? b[row + (int64_t)c * ld] - ax : ax;
     }
 }
@@ -1434,12 +1447,12 @@ __global__ __launch_bounds__(kBlock) void gs_color_push(const int64_t* __restric
         const double dg = diag[row];
         if (omega == 1.0) {
 #pragma unroll
-            for (int c = 0; c < D; ++c) { xn[c] = (b[row + (int64_t)c * ld] - acc[c]) / dg; x[row + (int64_t)c * ld] = xn[c]; }
+            for (int c = 0; c < D; ++c) { xn[c] = gs_row(b[row + (int64_t)c * ld], acc[c], dg); x[row + (int64_t)c * ld] = xn[c]; }
         } else {
 #pragma unroll
             for (int c = 0; c < D; ++c) {
                 const double xi = x[row + (int64_t)c * ld];
-                xn[c] = xi + omega * ((b[row + (int64_t)c * ld] - acc[c]) / dg - xi);
+                xn[c] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
                 x[row + (int64_t)c * ld] = xn[c];
             }
         }
@@ -1642,9 +1655,9 @@ __global__ __launch_bounds__(kBlock) void residual_norm_partials(const int64_t* 
 #pragma unroll
         for (int c = 0; c < D; ++c) {
             const double bi = b[row + (int64_t)c * ld];
-            const double r = acc[c] + dg * x[row + (int64_t)c * ld] - bi;
-            sums[2 * c] += (r * w) * r;
-            sums[2 * c + 1] += (bi * w) * bi;
+            const double r = row_ax(acc[c], dg, x[row + (int64_t)c * ld]) - bi;
+            sums[2 * c] += norm_term(r, w);
+            sums[2 * c + 1] += norm_term(bi, w);
         }
     }
 #pragma unroll
@@ -1697,26 +1710,13 @@ __global__ __launch_bounds__(kNormWaves * 64, 8) void residual_norm_slices(const
         for (int c = 0; c < D; ++c) {
             const double bi = b[row + (int64_t)c * ld];
             double r;
-            if (MODE == 1) { r = bi - (acc[c] + dg * x[row + (int64_t)c * ld]); r32[row + (int64_t)c * ld] = (float)r; }
-            else r = acc[c] + dg * x[row + (int64_t)c * ld] - bi;
-            sums[2 * c] = (r * w) * r;
-            sums[2 * c + 1] = (bi * w) * bi;
+            if (MODE == 1) { r = bi - row_ax(acc[c], dg, x[row + (int64_t)c * ld]); r32[row + (int64_t)c * ld] = (float)r; }
+            else r = row_ax(acc[c], dg, x[row + (int64_t)c * ld]) - bi;
+            sums[2 * c] = norm_term(r, w);
+            sums[2 * c + 1] = norm_term(bi, w);
         }
     }
-#pragma unroll
-    for (int c = 0; c < 2 * D; ++c) {
-        double v = sums[c];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-        if (lane == 0) red[wave][c] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2 * D) {
-        double v = 0.0;
-#pragma unroll
-        for (int w2 = 0; w2 < kNormWaves; ++w2) v += red[w2][threadIdx.x];
-        partials[(int64_t)bb * (2 * D) + threadIdx.x] = v;
-    }
+    block_sums_store<kNormWaves, D>(sums, red, wave, lane, bb, partials);
 }
 
 // ---- mixed precision (fp32 inner V-cycle inside an fp64 defect-correction loop, BASELINE config 5) ----------------
