@@ -47,6 +47,7 @@
 #include "kernels.hip.hpp"
 #include "setup_kernels.hip.hpp"
 #include "hierarchy_kernels.hip.hpp"
+#include "accel_kernels.hip.hpp"
 
 using namespace gmg;
 using clk = std::chrono::steady_clock;
@@ -142,6 +143,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->restrict_sigma = 64;
     cfg->gs_omega = 1.35;     // measured (profiles/r02/a_iteration_ab.json, f_iteration_ab_omega_scan.json): 7 -> 4 V-cycles to 1e-4 on the 3 M Poisson
                               // problem at the same cost per cycle; centre of the 1.3 - 1.4 plateau on six workloads
+    cfg->accelerate = 0;      // the plain solve loop (1..4: truncated GCR around the cycle, solve_common)
     return GMG_OK;
 } GMG_CATCH_0
 
@@ -160,6 +162,8 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     if (c.sigma < 0 || c.sigma % 64 || c.restrict_sigma < 0 || c.restrict_sigma % 64 || c.row_align <= 0 || c.row_align % 64 || c.pre_iters < 0 || c.post_iters < 0 ||
         c.reorder_fine < 0 || c.reorder_fine > 2 || c.inner_precision < 0 || c.inner_precision > 1 || c.block_rows < 0 || c.block_rows > gmgk::kBlockRows || c.block_rows % 64 || c.block_from_level < 0 || !(c.gs_omega > 0.0 && c.gs_omega < 2.0) || c.dist_shard_levels < 1 || c.dist_shard_levels > 2 || c.block_fine < 0 || c.block_fine > 1 || c.dist_exchange < 0 || c.dist_exchange > 2 ||
         (c.block_lanes != 0 && c.block_lanes != 1 && c.block_lanes != 4) || (c.block_lanes != 1 && c.block_rows > gmgk::kQuadBlockRows)) return GMG_ERR_INVALID;
+    if (c.accelerate < 0 || c.accelerate > gmg::kAccelMaxDepth) return GMG_ERR_INVALID;
+    if (c.accelerate > 0 && c.inner_precision) return GMG_ERR_UNSUPPORTED;      // the recombination is fp64 only (gmg_config::accelerate)
     gmg_handle h = new gmg_solver_s();
     h->cfg = c;
     if (h->cfg.host_threads <= 0) h->cfg.host_threads = hw_threads();
@@ -701,14 +705,47 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     // correctly rounded arithmetic: gmgk::reduce_partials / SolveWatch) and the first colour launch of the next cycle is enqueued behind it at
     // once -- it returns without touching x when the iteration has stopped.  The ~6 us the host needs to see the norm and to get a launch to
     // the device are hidden behind that launch.  The host follows the device's word (one decision, not two).
-    WatchScope watch(h, head_eligible(h, d), 1, tol, stop_type);
+    // gmg_config::accelerate = m > 0: every cycle's step is recombined with the last m - 1 (truncated GCR, the cycle as the preconditioner:
+    // launch_accel_step) so that the weighted residual this loop tests is minimal.  The residue then comes out of a recurrence (r -= alpha q); one that
+    // would end the loop is CONFIRMED by the ordinary check on the new iterate -- that value is the one reported and tested (the recurrence can
+    // drop below the accuracy floor of b - A x) -- and the loop goes on from the recomputed residual where it does not hold.  No speculated head:
+    // the host decides.
+    const int accel = h->cfg.accelerate;
+    int confirmations = 0;
+    if (accel > 0) {
+        if ((rc = ensure_accel(h))) return rc;
+        Level& l0 = h->lv[0];
+        HIPCHK(hipMemsetAsync(h->accel.scal, 0, sizeof(double) * ((size_t)8 * h->accel.d + 1), h->stream));      // nothing stored (s_j = 0), no guarded step
+        HIPCHK(hipMemcpyAsync(h->accel.xk, l0.x, sizeof(double) * (size_t)l0.n_pad * d, hipMemcpyDeviceToDevice, h->stream));
+        launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
+    }
+    WatchScope watch(h, accel == 0 && head_eligible(h, d), 1, tol, stop_type);
     do {
         h->watch_cycles_done = it + 1;
-        if ((rc = vcycle_resident(h, d, stop_type))) return rc;
-        const bool head = watch.on && it + 2 <= max_iter;          // (a cycle after this one is allowed)
-        if (head) enqueue_head(h, d);
-        if ((rc = wait_norm(h))) return rc;
-        residue = norm_from_sums(h->h_norm, d, stop_type);
+        const bool head = accel == 0 && watch.on && it + 2 <= max_iter;          // (a cycle after this one is allowed)
+        bool confirmed = false;
+        if (accel > 0) {
+            Level& l0 = h->lv[0];
+            if ((rc = vcycle_resident(h, d, -1))) return rc;
+            launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, l0.r);                  // r~ = b - A x~ (q = r - r~ = A z: no product of its own)
+            if ((rc = launch_accel_step(h, d, stop_type, it))) return rc;
+            if ((rc = wait_norm(h))) return rc;
+            residue = norm_from_sums(h->h_norm, d, stop_type);
+            const double least = it == 0 || residue < least_residue ? residue : least_residue;
+            const bool blown_now = !std::isfinite(residue) || (it + 1 >= 3 && residue > 1e4 * least);
+            if (!(residue > tol && it + 1 < max_iter && !blown_now)) {           // it would end the loop: the check on the iterate itself decides
+                if ((rc = launch_norm(h, d, stop_type))) return rc;
+                if ((rc = wait_norm(h))) return rc;
+                residue = norm_from_sums(h->h_norm, d, stop_type);
+                confirmed = true;
+                ++confirmations;
+            }
+        } else {
+            if ((rc = vcycle_resident(h, d, stop_type))) return rc;
+            if (head) enqueue_head(h, d);
+            if ((rc = wait_norm(h))) return rc;
+            residue = norm_from_sums(h->h_norm, d, stop_type);
+        }
         if (it == 0) first_residue = least_residue = residue;
         if (residue < least_residue) least_residue = residue;
         if (conv) { conv[2 * it] = ms_since(t0); conv[2 * it + 1] = residue; }
@@ -723,8 +760,19 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
             go_on = device_go;
             if (!go_on) h->head_enqueued = false;                  // that launch found the word cleared and returned
         }
+        // (the confirmed residue is above the tolerance: the recurrence restarts from the residual of the iterate, the directions stay)
+        if (confirmed && go_on) launch_spmv<double>(h, h->lv[0], d, 1, h->lv[0].b, h->lv[0].x, h->accel.r);
     } while (go_on);
     h->timing["cycles"] = ms_since(t0);
+    h->timing["accelerate"] = accel;
+    h->timing["accel_confirmations"] = confirmations;
+    h->timing["accel_guard_steps"] = 0.0;
+    if (accel > 0) {
+        double guard_steps = 0.0;
+        HIPCHK(hipMemcpyAsync(&guard_steps, h->accel.scal + (size_t)8 * h->accel.d, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        h->timing["accel_guard_steps"] = guard_steps;
+    }
     // Not contracting: the iteration ended above the tolerance with a residue that is not finite or larger than after the first cycle.
     // The parallel smoothers are not the reference's lexicographic Gauss-Seidel (block sweeps on the Galerkin levels take the
     // couplings between blocks from the previous sweep; nothing guarantees their convergence for every SPD matrix), so the caller
@@ -846,6 +894,7 @@ int gmg_dist_partition(gmg_handle h, int rank, int world) try {
     if (!h) return GMG_ERR_INVALID;
     PoolScope pool_scope_(&h->pool);
     if (world < 1 || rank < 0 || rank >= world) return fail(h, GMG_ERR_INVALID, "bad rank / world size");
+    if (world > 1 && h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only (create the handle with accelerate = 0)");
     if (world > 1 && h->cfg.row_align % (64 * world)) return fail(h, GMG_ERR_STATE, "create the handle with row_align = 64 * world (colour classes are cut into `world` pieces of whole slices)");
     if (rank == h->part_rank && world == h->part_world) return GMG_OK;
     if (h->has_device && h->live != LiveSystem::none) { drop_system(h); h->live_key_valid = false; }      // laid out for another partition
@@ -859,6 +908,7 @@ int gmg_dist_setup(gmg_handle h, int rank, int world) try {
     int rc = check_level(h, 0, false);
     if (rc) return rc;
     if (world < 1 || rank < 0 || rank >= world) return fail(h, GMG_ERR_INVALID, "bad rank / world size");
+    if (world > 1 && h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only (create the handle with accelerate = 0)");
     if (h->partitioned && (rank != h->part_rank || world != h->part_world)) return fail(h, GMG_ERR_STATE, "the system was laid out for another rank / world size (gmg_dist_partition)");
     const LevelOrdering& o = h->lv[0].ord;
     if (h->cfg.smoother != GMG_SMOOTHER_MULTICOLOR_GS) return fail(h, GMG_ERR_STATE, "the distributed path needs the multicolour / block-hybrid smoothers (gmg_config::smoother)");

@@ -449,16 +449,18 @@ int wait_norm(gmg_handle h) {
 }
 
 // the reduction of one group of <= 4 columns: into h_norm + flag when polled, into d_norm (+ a copy later) otherwise
-void launch_reduce(gmg_handle h, int nblk, int dc, int c0, bool last) {
+// (partials: whose block sums -- the norm kernels' by default)
+void launch_reduce(gmg_handle h, int nblk, int dc, int c0, bool last, const double* partials = nullptr) {
+    if (!partials) partials = h->d_partials;
     if (polled(h)) {
         gmgk::SolveWatch watch{nullptr, nullptr, nullptr, 0.0, 0, 0, 0, 0};
         if (h->watch_active && last && c0 == 0 && h->d_watch)         // (one group of columns: the kernel sees every sum the decision needs)
             watch = gmgk::SolveWatch{reinterpret_cast<int*>(h->d_watch + 1), h->h_flag + 1, h->d_watch, h->watch_tol, h->watch_mode, h->watch_type, dc, h->watch_cycles_done};
-        hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, h->d_partials, nblk, 2 * dc, h->h_norm + 2 * c0,
+        hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, partials, nblk, 2 * dc, h->h_norm + 2 * c0,
                            last ? h->h_flag : nullptr, last ? ++h->flag_seq[0] : 0ull, (int)EnvSwitches::get().publish_fenced, watch);
     }
     else
-        hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, h->d_partials, nblk, 2 * dc, h->d_norm + 2 * c0,
+        hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, partials, nblk, 2 * dc, h->d_norm + 2 * c0,
                            (unsigned long long*)nullptr, 0ull, 0);
 }
 
@@ -500,6 +502,7 @@ int ensure_vectors(gmg_handle h, int d) {
     if (d <= h->dcap) return GMG_OK;
     drop_graphs(h);
     unbind_level0(h);
+    drop_accel(h);
     for (auto& l : h->lv) {
         for (double** p : {&l.x, &l.b, &l.r, &l.tmp}) {
             if (*p) { (void)dev_free(*p); *p = nullptr; }
@@ -1038,6 +1041,63 @@ int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt) {
 int vcycle_resident(gmg_handle h, int d, int norm_type) {
     if (h->cfg.inner_precision) return vcycle_legs<float>(h, d, norm_type, 100000);
     return vcycle_legs<double>(h, d, norm_type, 0);
+}
+
+// ---- accelerated solve loop (gmg_config::accelerate; engine.hip::solve_common; kernels: accel_kernels.hip.hpp) ----------------------
+
+// its vectors and scalars, for the level vectors as they are now (n_pad x dcap)
+int ensure_accel(gmg_handle h) {
+    auto& a = h->accel;
+    const int m = h->cfg.accelerate, n_pad = h->lv[0].n_pad, D = h->dcap;
+    if (a.xk && a.depth == m && a.d == D && a.n_pad == n_pad) return GMG_OK;
+    drop_accel(h);
+    const size_t bytes = sizeof(double) * (size_t)n_pad * D;
+    auto vec = [&](double** p) -> int {
+        HIPCHK(dev_malloc((void**)p, bytes));
+        HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));          // (padding rows: zero, and no kernel writes anything else there)
+        return GMG_OK;
+    };
+    int rc;
+    for (double** p : {&a.xk, &a.r, &a.z0}) if ((rc = vec(p))) return rc;
+    for (int j = 0; j < m - 1; ++j) for (double** p : {&a.zs[j], &a.qs[j]}) if ((rc = vec(p))) return rc;
+    HIPCHK(dev_malloc((void**)&a.scal, sizeof(double) * ((size_t)8 * D + 1)));
+    HIPCHK(dev_malloc((void**)&a.partials, sizeof(double) * (size_t)gmgk::kAccelMaxBlocks * gmgk::kAccelMaxComp));
+    a.depth = m; a.d = D; a.n_pad = n_pad;
+    return GMG_OK;
+}
+
+// One recombination: lv[0].x holds the cycle's iterate x~, lv[0].r its residual b - A x~; `done` directions were formed in this solve before this
+// one.  Leaves the new iterate in lv[0].x (and accel.xk), the recurrence residual in accel.r and the check's sums on their way to h_norm (wait_norm).
+int launch_accel_step(gmg_handle h, int d, int type, int done) {
+    auto& a = h->accel;
+    Level& l = h->lv[0];
+    const int DA = a.d, ld = l.n_pad, n_pairs = l.n_pad / 2, stored = a.depth - 1;
+    const int ns = std::min(done, stored);                       // stored directions to orthogonalise against
+    const int wslot = stored > 0 ? done % stored : -1;           // ring slot the new direction replaces (the oldest, or a free one)
+    const int nblk = std::max(1, std::min(gmgk::kAccelMaxBlocks, (n_pairs + gmgk::kAccelBlock - 1) / gmgk::kAccelBlock));
+    const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
+    double *alpha = a.scal, *guarded = a.scal + DA, *beta = a.scal + 2 * DA, *s_slot = a.scal + 5 * DA, *guard_steps = a.scal + 8 * DA;
+    for_col_chunks(d, [&](int c0, int dc) {
+        const size_t off = (size_t)c0 * ld;
+        gmgk::AccelRing ring{};
+        for (int j = 0; j < ns; ++j) { ring.z[j] = a.zs[j] + off; ring.q[j] = a.qs[j] + off; }
+        double* q0 = l.r + off;
+        double* zw = wslot >= 0 ? a.zs[wslot] + off : nullptr;
+        double* qw = wslot >= 0 ? a.qs[wslot] + off : nullptr;
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::accel_form<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, l.x + off, a.xk + off, a.r + off, q0, a.z0 + off,
+                                          ring, ns, w, ld, n_pairs, a.partials));
+        if (ns > 0)
+            hipLaunchKernelGGL(gmgk::accel_reduce_beta, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, ns, dc, s_slot + c0, DA, beta + c0);
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::accel_orth<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.z0 + off, q0, a.r + off, ring, ns, zw, qw,
+                                          beta + c0, DA, w, ld, n_pairs, a.partials));
+        hipLaunchKernelGGL(gmgk::accel_reduce_alpha, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, alpha + c0, guarded + c0,
+                           wslot >= 0 ? s_slot + (size_t)wslot * DA + c0 : nullptr, guard_steps);
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::accel_update<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.xk + off, l.x + off, a.r + off,
+                                          zw ? zw : a.z0 + off, qw ? qw : q0, a.z0 + off, q0, alpha + c0, guarded + c0, l.b + off, w, ld, n_pairs, a.partials));
+        launch_reduce(h, nblk, dc, c0, c0 + 4 >= d, a.partials);
+    });
+    if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
+    return GMG_OK;
 }
 
 int check_level(gmg_handle h, int k, bool allow_coarsest) {

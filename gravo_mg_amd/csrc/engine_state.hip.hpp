@@ -232,6 +232,20 @@ struct gmg_solver_s {
     hipEvent_t h_chunk_ev[16] = {};      // per-chunk arrival of a download (to_host): 8 per staging buffer
     double* d_partials = nullptr; int partial_blocks = 0;
     double* d_norm = nullptr;
+    // The accelerated solve loop (gmg_config::accelerate = m > 0; engine.hip::solve_common): 2 (m - 1) + 3 level-0 vectors (n_pad x d) from the
+    // pool -- the previous iterate, the recurrence residual, the raw step z0, and the ring of m - 1 stored directions (z_j, q_j = A z_j) -- plus the
+    // device-side scalars and the partial sums of its kernels.  Allocated by the first accelerated solve (ensure_accel), released with the level
+    // vectors (drop_accel: ensure_vectors, drop_system).
+    struct AccelState {
+        double *xk = nullptr, *r = nullptr, *z0 = nullptr;
+        double* zs[gmg::kAccelMaxStored] = {};
+        double* qs[gmg::kAccelMaxStored] = {};
+        double* scal = nullptr;          // alpha[d], guarded[d], beta[3][d], s_j[3][d], guarded steps of the solve: 8 d + 1 doubles
+                                         // (s_j = 0: slot j holds no usable direction for that column -- never stored, or stored by a guarded step:
+                                         // its vector entries may be anything and are not looked at, accel_kernels.hip.hpp::AccelRing)
+        double* partials = nullptr;      // kAccelMaxBlocks x kAccelMaxComp
+        int depth = 0, d = 0, n_pad = 0;
+    } accel;
     // Head of the next cycle (gmg_config::speculate_head; engine.hip::solve_common): the solve loop's decision is taken by the check's
     // reduction on the device (d_watch: {double least; int go}), the first colour launch of the next cycle is enqueued behind it before the
     // host has seen the norm, and returns at once when the iteration stopped.  watch_*: what the reduction needs to decide; head_enqueued:
@@ -579,6 +593,14 @@ void free_level(Level& l) {
     if (l.d_blk_of_row) { (void)dev_free(l.d_blk_of_row); l.d_blk_of_row = nullptr; }
 }
 
+// the vectors and scalars of the accelerated solve loop (gmg_solver_s::AccelState)
+void drop_accel(gmg_handle h) {
+    auto& a = h->accel;
+    for (double** p : {&a.xk, &a.r, &a.z0, &a.scal, &a.partials}) { if (*p) (void)dev_free(*p); *p = nullptr; }
+    for (int j = 0; j < gmg::kAccelMaxStored; ++j) for (double** p : {&a.zs[j], &a.qs[j]}) { if (*p) (void)dev_free(*p); *p = nullptr; }
+    a.depth = a.d = a.n_pad = 0;
+}
+
 void drop_graphs(gmg_handle h) {
     for (auto& kv : h->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     h->graphs.clear();
@@ -596,6 +618,7 @@ void drop_system(gmg_handle h) {
     lose_live_system(h);
     drop_graphs(h);
     unbind_level0(h);
+    drop_accel(h);
     h->dist_ready = false;
     for (auto& l : h->lv) free_level(l);
     h->lv.clear();

@@ -137,6 +137,17 @@ typedef struct {
     int color_ahead;       /* 1 (default): a gmg_set_system that cannot be a values-only refresh starts the greedy colouring of level 0 (one core, 10-13 ms at
                               3 M vertices: the longest task of a cold set-up) at entry, beside the inspection of the caller's arrays, with every index checked;
                               the result is used when the inspection and the layout decisions allow it -- the same colours, ~6 ms earlier.  0: after them */
+    int accelerate;        /* 0 (default): the solve loop as in the reference (cycle, residual check, repeat).  m in 1..4: gmg_solve, gmg_solve_x0_rhs and
+                              gmg_solve_device recombine the iterates by truncated GCR with the V-cycle as the preconditioner: every cycle's step is
+                              orthogonalised (in the stop type's weighted inner product, per right-hand-side column) against the last m - 1 stored
+                              directions and scaled so that the weighted residual the loop tests is minimal -- that residue cannot grow (m = 1: a plain
+                              minimal-residual step length).  The residue that ends the loop is confirmed by the ordinary residual check on the iterate
+                              the caller gets.  2 (m - 1) + 3 more level-0 vectors on the device; fp64 only: with inner_precision = 1 gmg_create returns
+                              GMG_ERR_UNSUPPORTED; outside 0..4 GMG_ERR_INVALID.  One device only: on such a handle gmg_p2p_prepare, and gmg_dist_setup /
+                              gmg_dist_partition with world > 1, return GMG_ERR_UNSUPPORTED.  Unchanged by this field: gmg_run_cycles, gmg_vcycle,
+                              gmg_profile_cycle and the operator entry points (gmg_smooth, gmg_residual_norm, ...).  Every solve writes the timing keys
+                              "accelerate" (m), "accel_confirmations" and "accel_guard_steps" (columns x iterations that took the cycle's own iterate
+                              because <q, q> was zero or not finite) -- with accelerate = 0 too, as zeros: the only trace of this field on the default path */
 } gmg_config;
 
 /* ---- lifetime ------------------------------------------------------------------------------- */
