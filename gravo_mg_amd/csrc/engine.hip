@@ -7,7 +7,7 @@
 // the device from that factor; gmg_config::coarse_mode = GMG_COARSE_AUTO, the default) or back-substituted on the host.
 //
 // One translation unit: engine_state.hip.hpp (memory pool, level / handle structures, helpers), engine_setup.hip.hpp
-// (device-side layout construction, Galerkin products), engine_cycle.hip.hpp (launch helpers, V-cycle legs),
+// (device-side layout construction, Galerkin products), engine_cycle.hip.hpp (launch helpers, V-cycle legs, the solve loop),
 // engine_dist.hip.hpp / engine_part.hip.hpp (multi-GPU cycle, partition plan), engine_system.hip.hpp (the set-up stages
 // of gmg_set_system) and this file (the extern "C" entry points).
 //
@@ -691,107 +691,75 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     if (bad_args) return fail(h, GMG_ERR_INVALID, bad_args);
     if ((rc = check_whole_system(h))) return rc;
     if ((rc = check_norm_type(h, stop_type))) return rc;
-    if (max_iter < 1) max_iter = 1;      // do { } while: at least one cycle (multigrid_solver.cpp:1411-1417)
     auto t_all = clk::now();
     HelperScope helper_scope(h, d);
     if ((rc = load())) return rc;
     h->timing["solve_load"] = ms_since(t_all);
     h->timing["coarse_host_ms"] = 0.0;
     auto t0 = clk::now();
-    double residue = 0.0, first_residue = 0.0, least_residue = 0.0;
-    int it = 0;
-    bool blown = false, go_on = false;
-    // Head of the next cycle (gmg_config::speculate_head): the check's reduction takes the decision below on the device too (same sums, same
-    // correctly rounded arithmetic: gmgk::reduce_partials / SolveWatch) and the first colour launch of the next cycle is enqueued behind it at
-    // once -- it returns without touching x when the iteration has stopped.  The ~6 us the host needs to see the norm and to get a launch to
-    // the device are hidden behind that launch.  The host follows the device's word (one decision, not two).
     // gmg_config::accelerate = m > 0: every cycle's step is recombined with the last m - 1 (truncated GCR, the cycle as the preconditioner:
-    // launch_accel_step) so that the weighted residual this loop tests is minimal.  The residue then comes out of a recurrence (r -= alpha q); one that
+    // launch_accel_step) so that the weighted residual the loop tests is minimal.  The residue then comes out of a recurrence (r -= alpha q); one that
     // would end the loop is CONFIRMED by the ordinary check on the new iterate -- that value is the one reported and tested (the recurrence can
     // drop below the accuracy floor of b - A x) -- and the loop goes on from the recomputed residual where it does not hold.  No speculated head:
     // the host decides.
     const int accel = h->cfg.accelerate;
     int confirmations = 0;
+    Level& l0 = h->lv[0];
+    auto accel_step = [&](const SolveRule& rule, double& residue, int&) -> int {
+        if ((rc = vcycle_resident(h, d, -1))) return rc;
+        launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, l0.r);                  // r~ = b - A x~ (q = r - r~ = A z: no product of its own)
+        if ((rc = launch_accel_step(h, d, stop_type, rule.cycles))) return rc;
+        if ((rc = wait_norm(h))) return rc;
+        residue = norm_from_sums(h->h_norm, d, stop_type);
+        if (rule_goes_on(rule_after(rule, residue))) return GMG_OK;
+        if ((rc = launch_norm(h, d, stop_type))) return rc;                   // it would end the loop: the check on the iterate itself decides
+        if ((rc = wait_norm(h))) return rc;
+        residue = norm_from_sums(h->h_norm, d, stop_type);
+        ++confirmations;
+        // (confirmed, above the tolerance and the loop will go on: the recurrence restarts from the residual of the iterate, the directions stay)
+        if (rule_goes_on(rule_after(rule, residue))) launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
+        return GMG_OK;
+    };
+    // Head of the next cycle (gmg_config::speculate_head): the check's reduction takes the loop's decision on the device too (same sums, same
+    // functions: gmgk::reduce_partials / SolveWatch, solve_rule.hpp) and the first colour launch of the next cycle is enqueued behind it at
+    // once -- it returns without touching x when the iteration has stopped.  The ~6 us the host needs to see the norm and to get a launch to
+    // the device are hidden behind that launch.  The loop follows the device's word.
+    WatchScope watch(h, accel == 0 && head_eligible(h, d), 1, tol, stop_type);
+    auto plain_step = [&](const SolveRule& rule, double& residue, int& device_go) -> int {
+        h->watch_cycles_done = rule.cycles + 1;
+        const bool head = watch.on && rule.cycles + 2 <= rule.max_iter;          // (a cycle after this one is allowed)
+        if ((rc = vcycle_resident(h, d, stop_type))) return rc;
+        if (head) enqueue_head(h, d);
+        if ((rc = wait_norm(h))) return rc;
+        residue = norm_from_sums(h->h_norm, d, stop_type);
+        if (head) device_go = __atomic_load_n(h->h_flag + 1, __ATOMIC_ACQUIRE) != 0;
+        if (device_go == 0) h->head_enqueued = false;                  // that launch found the word cleared and returned
+        return GMG_OK;
+    };
+    int verdict;
     if (accel > 0) {
         if ((rc = ensure_accel(h))) return rc;
-        Level& l0 = h->lv[0];
         HIPCHK(hipMemsetAsync(h->accel.scal, 0, sizeof(double) * ((size_t)8 * h->accel.d + 1), h->stream));      // nothing stored (s_j = 0), no guarded step
         HIPCHK(hipMemcpyAsync(h->accel.xk, l0.x, sizeof(double) * (size_t)l0.n_pad * d, hipMemcpyDeviceToDevice, h->stream));
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
-    }
-    WatchScope watch(h, accel == 0 && head_eligible(h, d), 1, tol, stop_type);
-    do {
-        h->watch_cycles_done = it + 1;
-        const bool head = accel == 0 && watch.on && it + 2 <= max_iter;          // (a cycle after this one is allowed)
-        bool confirmed = false;
-        if (accel > 0) {
-            Level& l0 = h->lv[0];
-            if ((rc = vcycle_resident(h, d, -1))) return rc;
-            launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, l0.r);                  // r~ = b - A x~ (q = r - r~ = A z: no product of its own)
-            if ((rc = launch_accel_step(h, d, stop_type, it))) return rc;
-            if ((rc = wait_norm(h))) return rc;
-            residue = norm_from_sums(h->h_norm, d, stop_type);
-            const double least = it == 0 || residue < least_residue ? residue : least_residue;
-            const bool blown_now = !std::isfinite(residue) || (it + 1 >= 3 && residue > 1e4 * least);
-            if (!(residue > tol && it + 1 < max_iter && !blown_now)) {           // it would end the loop: the check on the iterate itself decides
-                if ((rc = launch_norm(h, d, stop_type))) return rc;
-                if ((rc = wait_norm(h))) return rc;
-                residue = norm_from_sums(h->h_norm, d, stop_type);
-                confirmed = true;
-                ++confirmations;
-            }
-        } else {
-            if ((rc = vcycle_resident(h, d, stop_type))) return rc;
-            if (head) enqueue_head(h, d);
-            if ((rc = wait_norm(h))) return rc;
-            residue = norm_from_sums(h->h_norm, d, stop_type);
-        }
-        if (it == 0) first_residue = least_residue = residue;
-        if (residue < least_residue) least_residue = residue;
-        if (conv) { conv[2 * it] = ms_since(t0); conv[2 * it + 1] = residue; }
-        ++it;
-        if (h->cfg.verbose) std::printf("%d,%f,%.14f \n", it, ms_since(t0), residue);
-        // no way back from here (the reference would spin to max_iter on NaNs): stop, the caller is told below
-        blown = !std::isfinite(residue) || (it >= 3 && residue > 1e4 * least_residue);
-        go_on = residue > tol && it < max_iter && !blown;
-        if (head) {
-            const bool device_go = __atomic_load_n(h->h_flag + 1, __ATOMIC_ACQUIRE) != 0;
-            if (device_go != go_on) h->timing["head_decision_differs"] += 1.0;      // (never seen: the two sides compute the same bits)
-            go_on = device_go;
-            if (!go_on) h->head_enqueued = false;                  // that launch found the word cleared and returned
-        }
-        // (the confirmed residue is above the tolerance: the recurrence restarts from the residual of the iterate, the directions stay)
-        if (confirmed && go_on) launch_spmv<double>(h, h->lv[0], d, 1, h->lv[0].b, h->lv[0].x, h->accel.r);
-    } while (go_on);
-    h->timing["cycles"] = ms_since(t0);
+        verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, accel_step);
+    } else
+        verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, plain_step);
+    if (verdict < 0) return verdict;
     h->timing["accelerate"] = accel;
     h->timing["accel_confirmations"] = confirmations;
-    h->timing["accel_guard_steps"] = 0.0;
+    double guard_steps = 0.0;
     if (accel > 0) {
-        double guard_steps = 0.0;
         HIPCHK(hipMemcpyAsync(&guard_steps, h->accel.scal + (size_t)8 * h->accel.d, sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        h->timing["accel_guard_steps"] = guard_steps;
     }
-    // Not contracting: the iteration ended above the tolerance with a residue that is not finite or larger than after the first cycle.
-    // The parallel smoothers are not the reference's lexicographic Gauss-Seidel (block sweeps on the Galerkin levels take the
-    // couplings between blocks from the previous sweep; nothing guarantees their convergence for every SPD matrix), so the caller
-    // is told -- return value GMG_DIVERGED and timing key "diverged" -- and can retry on a handle with block_rows = 0, gs_omega = 1:
-    // Gauss-Seidel in colour order on every level, convergent for every SPD matrix (MultigridSolver::solve does).  x receives the
-    // last iterate either way, as in the reference (multigrid_solver.cpp:1408-1419 never looks at the trend).
-    bool diverged = !(residue <= tol) && (blown || (it > 1 && residue > first_residue));
-    h->timing["diverged"] = diverged ? 1.0 : 0.0;
-    h->timing["blown_up"] = blown ? 1.0 : 0.0;           // stopped early: residue not finite or 1e4 x the smallest seen
+    h->timing["accel_guard_steps"] = guard_steps;
     auto t_f = clk::now();
     if ((rc = fetch())) return rc;
     h->timing["solve_fetch"] = ms_since(t_f);
-    h->timing["iterations"] = it;
-    h->timing["residue"] = residue;
     h->timing["solve_call"] = ms_since(t_all);
     h->timing["solver_total"] = h->timing["setup_total"] + h->timing["solve_call"];
-    if (iters_out) *iters_out = it;
-    if (residue_out) *residue_out = residue;
-    return diverged ? GMG_DIVERGED : GMG_OK;
+    return verdict;
 }
 }  // extern "C++"
 

@@ -484,20 +484,6 @@ int launch_norm(gmg_handle h, int d, int type) {
     return GMG_OK;
 }
 
-double norm_from_sums(const double* s, int d, int type) {
-    if (type == 3) {
-        double t = 0.0;
-        for (int c = 0; c < d; ++c) t += s[2 * c];
-        return std::sqrt(t);
-    }
-    double out = 0.0;
-    for (int c = 0; c < d; ++c) {
-        double v = type == 0 ? std::sqrt(s[2 * c]) / std::sqrt(s[2 * c + 1]) : std::sqrt(s[2 * c] / s[2 * c + 1]);
-        if (c == 0 || v > out) out = v;
-    }
-    return out;
-}
-
 int ensure_vectors(gmg_handle h, int d) {
     if (d <= h->dcap) return GMG_OK;
     drop_graphs(h);
@@ -1098,6 +1084,42 @@ int launch_accel_step(gmg_handle h, int d, int type, int done) {
     });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
+}
+
+// ---- the solve loop (gmg_solve, gmg_solve_x0_rhs, gmg_solve_device, gmg_p2p_solve) -----------------------------------------------------
+// do { one cycle; the stopping rule of solve_rule.hpp } while (it goes on).  What a cycle is, is the caller's: step(rule, residue, device_go)
+// advances one cycle from the state `rule` and reports its residue -- and, where the check's reduction took the decision on the device
+// (gmgk::reduce_partials, the same functions on the same sums), that word in device_go (0 / 1): the loop follows it, one decision, not two.
+// conv (optional): (ms since t0, residue) pairs.  Sets the timing keys cycles, diverged, blown_up, iterations and residue and the two
+// outputs; returns GMG_OK, GMG_DIVERGED or what a step failed with (< 0).
+template <class Step>
+int solve_loop(gmg_handle h, double tol, int max_iter, clk::time_point t0, double* conv, bool verbose, int* iters_out, double* residue_out, Step&& step) {
+    SolveRule rule = rule_begin(tol, max_iter);
+    bool go_on;
+    do {
+        double residue = 0.0; int device_go = -1;          // (-1: the host decides)
+        if (const int rc = step(rule, residue, device_go)) return rc;
+        rule = rule_after(rule, residue);
+        if (conv) { conv[2 * rule.cycles - 2] = ms_since(t0); conv[2 * rule.cycles - 1] = residue; }
+        if (verbose) std::printf("%d,%f,%.14f \n", rule.cycles, ms_since(t0), residue);
+        go_on = rule_goes_on(rule);
+        if (device_go >= 0) {
+            if ((device_go != 0) != go_on) h->timing["head_decision_differs"] += 1.0;      // (never seen: the two sides compute the same bits)
+            go_on = device_go != 0;
+        }
+    } while (go_on);
+    h->timing["cycles"] = ms_since(t0);
+    // Not contracting.  The parallel smoothers are not the reference's lexicographic Gauss-Seidel (block sweeps on the Galerkin levels take the
+    // couplings between blocks from the previous sweep; nothing guarantees their convergence for every SPD matrix), so the caller is told --
+    // return value GMG_DIVERGED and timing key "diverged" -- and can retry on a handle with block_rows = 0, gs_omega = 1: Gauss-Seidel in
+    // colour order on every level, convergent for every SPD matrix (MultigridSolver::solve does).  x receives the last iterate either way, as
+    // in the reference (multigrid_solver.cpp:1408-1419 never looks at the trend).
+    const bool diverged = rule_diverged(rule);
+    h->timing["diverged"] = diverged ? 1.0 : 0.0; h->timing["blown_up"] = rule.blown ? 1.0 : 0.0;           // (blown_up: stopped early)
+    h->timing["iterations"] = rule.cycles; h->timing["residue"] = rule.residue;
+    if (iters_out) *iters_out = rule.cycles;
+    if (residue_out) *residue_out = rule.residue;
+    return diverged ? GMG_DIVERGED : GMG_OK;
 }
 
 int check_level(gmg_handle h, int k, bool allow_coarsest) {

@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "solve_rule.hpp"
 
 namespace gmgk {
 
@@ -1260,9 +1261,9 @@ __device__ __forceinline__ void block_reduce_partials(const double* __restrict__
 // flag != nullptr: `out` is host-visible pinned memory and `seq` is published in *flag after the sums -- the host polls
 // that word instead of paying a copy kernel and a stream synchronisation per residual check.  (The sums are written by the
 // threads of wave 0; lane 0 of that wave releases them: one system-scope fence, not one per thread.)
-// The solve loop's decision, taken where the sums are (`watch.go` != nullptr): the host's arithmetic (engine_cycle.hip.hpp::norm_from_sums and the
-// loop of engine.hip::solve_common: sqrt and division are correctly rounded on both sides), so that a launch enqueued behind this one can be
-// told whether the iteration goes on.  The host does not decide a second time: it reads the word this kernel publishes beside the sums.
+// The solve loop's decision, taken where the sums are (`watch.go` != nullptr): the functions the host loop calls (solve_rule.hpp), so that a
+// launch enqueued behind this one can be told whether the iteration goes on.  The host does not decide a second time: it reads the word this
+// kernel publishes beside the sums.
 struct SolveWatch {
     int* go;                    // device word the speculative launch reads (nullptr: no decision wanted)
     unsigned long long* host_go;  // the same decision for the host (pinned, beside the sequence word)
@@ -1286,22 +1287,10 @@ __global__ __launch_bounds__(kReduceBlock) void reduce_partials(const double* __
                 for (int w = 0; w < kReduceBlock / 64; ++w) t += red[w][c];
                 s[c] = t;
             }
-            double res = 0.0;
-            if (watch.norm_type == 3) {
-                double t = 0.0;
-                for (int c = 0; c < watch.d; ++c) t += s[2 * c];
-                res = __builtin_sqrt(t);
-            } else {
-                for (int c = 0; c < watch.d; ++c) {
-                    const double v = watch.norm_type == 0 ? __builtin_sqrt(s[2 * c]) / __builtin_sqrt(s[2 * c + 1]) : __builtin_sqrt(s[2 * c] / s[2 * c + 1]);
-                    if (c == 0 || v > res) res = v;
-                }
-            }
-            double least = watch.cycles_done <= 1 ? res : *watch.least;
-            if (res < least) least = res;
+            const double res = gmg::norm_from_sums(s, watch.d, watch.norm_type);
+            const double least = gmg::rule_least(*watch.least, res, watch.cycles_done);
             *watch.least = least;
-            const bool blown = !__builtin_isfinite(res) || (watch.cycles_done >= 3 && res > 1e4 * least);
-            go = (res > watch.tol && !blown) ? 1 : 0;
+            go = gmg::rule_wants_more(res, watch.tol, gmg::rule_blown(res, least, watch.cycles_done)) ? 1 : 0;
         }
         *watch.go = go;
         __hip_atomic_store(watch.host_go, (unsigned long long)go, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

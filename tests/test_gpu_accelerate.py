@@ -73,7 +73,7 @@ def _weights(P, stop_type):
 
 
 def _norm(rr, bb, stop_type):
-    """engine_cycle.hip.hpp::norm_from_sums on the per-column sums of w r^2 and w b^2."""
+    """solve_rule.hpp::norm_from_sums on the per-column sums of w r^2 and w b^2."""
     if stop_type == 3:
         return float(np.sqrt(rr.sum()))
     with np.errstate(invalid="ignore", divide="ignore"):
