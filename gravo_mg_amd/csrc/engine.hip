@@ -44,6 +44,7 @@
 #include "host_plan.hpp"
 #include "host_sparse.hpp"
 #include "device_io_check.hpp"
+#include "cheby_coeffs.hpp"
 #include "kernels.hip.hpp"
 #include "setup_kernels.hip.hpp"
 #include "hierarchy_kernels.hip.hpp"
@@ -163,6 +164,7 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
         c.reorder_fine < 0 || c.reorder_fine > 2 || c.inner_precision < 0 || c.inner_precision > 1 || c.block_rows < 0 || c.block_rows > gmgk::kBlockRows || c.block_rows % 64 || c.block_from_level < 0 || !(c.gs_omega > 0.0 && c.gs_omega < 2.0) || c.dist_shard_levels < 1 || c.dist_shard_levels > 2 || c.block_fine < 0 || c.block_fine > 1 || c.dist_exchange < 0 || c.dist_exchange > 2 ||
         (c.block_lanes != 0 && c.block_lanes != 1 && c.block_lanes != 4) || (c.block_lanes != 1 && c.block_rows > gmgk::kQuadBlockRows)) return GMG_ERR_INVALID;
     if (c.accelerate < 0 || c.accelerate > gmg::kAccelMaxDepth) return GMG_ERR_INVALID;
+    if (c.smoother < GMG_SMOOTHER_MULTICOLOR_GS || c.smoother > GMG_SMOOTHER_CHEBYSHEV) return GMG_ERR_INVALID;
     if (c.accelerate > 0 && c.inner_precision) return GMG_ERR_UNSUPPORTED;      // the recombination is fp64 only (gmg_config::accelerate)
     gmg_handle h = new gmg_solver_s();
     h->cfg = c;
@@ -879,7 +881,7 @@ int gmg_dist_setup(gmg_handle h, int rank, int world) try {
     if (world > 1 && h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only (create the handle with accelerate = 0)");
     if (h->partitioned && (rank != h->part_rank || world != h->part_world)) return fail(h, GMG_ERR_STATE, "the system was laid out for another rank / world size (gmg_dist_partition)");
     const LevelOrdering& o = h->lv[0].ord;
-    if (h->cfg.smoother != GMG_SMOOTHER_MULTICOLOR_GS) return fail(h, GMG_ERR_STATE, "the distributed path needs the multicolour / block-hybrid smoothers (gmg_config::smoother)");
+    if (h->cfg.smoother != GMG_SMOOTHER_MULTICOLOR_GS) return fail(h, GMG_ERR_STATE, std::string("the distributed path needs the multicolour / block-hybrid smoothers (gmg_config::smoother), this handle runs ") + smoother_name(h->cfg));
     // a blocked level 0 (gmg_config::block_fine: kNN operators) is ONE class of rows cut into `world` runs of whole 64-row blocks
     if (o.blocked && (h->cfg.block_rows != 64 || !h->lv[0].use_ep)) return fail(h, GMG_ERR_STATE, "a blocked level 0 is partitioned only as 64-row blocks of the entry-parallel sweep (block_rows = 64, block_ep = 1, one lane per row): set block_fine = 0 or block_lanes = 1");
     for (int c = 0; c < dist_classes(o); ++c)
@@ -1076,10 +1078,10 @@ int gmg_bench_kernel(gmg_handle h, int kind, int k, int d, int reps, double* ms_
     Level& l = h->lv[k];
     int launches = 1;
     const bool il = k == 0 && d > 1 && d <= 4 && l.Aoff.lpr == 1;
-    const bool il_p = il && h->L >= 2 && h->lv[1].ord.blocked && h->lv[1].use_ep && h->cfg.post_iters > 0 && h->cfg.smoother != GMG_SMOOTHER_JACOBI;
+    const bool il_p = il && h->L >= 2 && h->lv[1].ord.blocked && h->lv[1].use_ep && h->cfg.post_iters > 0 && !pointwise_smoother(h->cfg);
     auto body = [&]() {
         switch (kind) {
-            case 0: launch_smooth<double>(h, l, d, 2); launches = (h->cfg.smoother == GMG_SMOOTHER_JACOBI || l.ord.blocked) ? 1 : l.ord.n_colors; break;
+            case 0: launch_smooth<double>(h, l, d, 2); launches = (pointwise_smoother(h->cfg) || l.ord.blocked) ? 1 : l.ord.n_colors; break;
             // (level 0 with 2 .. 4 right-hand sides: the variants the cycle runs -- residual written / gathered as an interleaved multi-vector,
             // prolongation from the interleaved copy of level 1's x: engine_cycle.hip.hpp::enqueue_down / enqueue_up)
             case 1: launch_spmv<double>(h, l, d, 1, l.b, l.x, l.r, -1, il); break;
@@ -1491,6 +1493,13 @@ int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const doubl
 int gmg_debug_set(gmg_handle h, const char* key, double value) try {
     if (!h || !key) return GMG_ERR_INVALID;
     if (std::string(key) == "col16_uncovered") { h->dbg_col16_uncovered = (int)value; return GMG_OK; }
+    if (std::string(key) == "cheby_ratio") {
+        if (value != 0.0 && !cheby_ratio_usable(value)) return fail(h, GMG_ERR_INVALID, "cheby_ratio must be > 1 (0: the process-wide ratio)");
+        h->dbg_cheby_ratio = value;
+        if (h->has_device) drop_graphs(h);                                         // (the coefficients are arguments of the captured launches)
+        if (h->timing.count("cheby_ratio")) h->timing["cheby_ratio"] = cheby_ratio(h);
+        return GMG_OK;
+    }
     return fail(h, GMG_ERR_INVALID, std::string("unknown debug key: ") + key);
 } GMG_CATCH_H
 

@@ -178,6 +178,31 @@ void launch_jacobi_sweeps(gmg_handle h, Level& l, int d, int iters) {
     if (in != Prec<T>::x(l)) (void)hipMemcpyAsync(Prec<T>::x(l), in, sizeof(T) * (size_t)ld * d, hipMemcpyDeviceToDevice, h->stream);
 }
 
+// `iters` steps of a Chebyshev polynomial that starts here (cheby_coeffs.hpp): one launch per step and group of columns, the step's two
+// coefficients as kernel arguments.  x ping-pongs between the level's x and tmp like the Jacobi sweeps; p lives in the level's residual vector,
+// which is dead while the level is smoothed (the way down forms b - A x after the pre-smoothing, the restriction has consumed it before the
+// post-smoothing, and the accelerated loop writes it anew after the cycle).
+template <class T>
+void launch_cheby_steps(gmg_handle h, Level& l, int d, int iters) {
+    const int ld = l.n_pad;
+    T* in = Prec<T>::x(l); T* out = Prec<T>::tmp(l);
+    const T* b = Prec<T>::b(l);
+    T* p = Prec<T>::r(l);
+    const int c16 = &l == &h->lv[0] ? l.Aoff.c16_sel() : 0;
+    const double ratio = cheby_ratio(h);
+    for (int it = 0; it < iters; ++it) {
+        const ChebyStep st = cheby_step_coeffs(l.cheby_lambda, ratio, it);
+        for_col_chunks(d, [&](int c0, int dc) {
+            DISPATCH_D(dc, DISPATCH_C16(c16, DISPATCH_FLAG(FIRST, it == 0, hipLaunchKernelGGL((gmgk::cheby_step<T, D, FIRST, C16>), dim3(grid_for(l.Aoff.n_slices)),
+                                              dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
+                                              in + (size_t)c0 * ld, out + (size_t)c0 * ld, p + (size_t)c0 * ld, ld, l.Aoff.n_slices, (T)st.c1, (T)st.c2, 1, l.Aoff.col16,
+                                              l.Aoff.win_base, l.Aoff.c16_arg()))));
+        });
+        std::swap(in, out);
+    }
+    if (in != Prec<T>::x(l)) (void)hipMemcpyAsync(Prec<T>::x(l), in, sizeof(T) * (size_t)ld * d, hipMemcpyDeviceToDevice, h->stream);
+}
+
 // Does the entry-parallel block sweep of level l STREAM its operator (non-temporal loads)?  Yes when the operator's chunks (12 B per explicit,
 // 10 B per lower entry in fp64) are more than the memory-side cache (256 MB on MI355X) holds beside the cycle's vectors between two of the
 // launches that read them: level 0 of a point cloud (300 MB) -- measured 0.634 ms per cycle streamed, 0.699 with ordinary loads; the 506 k-row
@@ -266,7 +291,7 @@ void launch_block_sweeps(gmg_handle h, Level& l, int d, int iters, bool from_zer
 // (begin_table / nb_list: an explicit list of blocks -- a rank's blocks of a partitioned level -- instead of all of them)
 template <class T>
 bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const int* begin_table = nullptr, int nb_list = 0) {
-    if (!l.use_ep || !h->sweep_prev_valid || h->cfg.smoother == GMG_SMOOTHER_JACOBI) return false;
+    if (!l.use_ep || !h->sweep_prev_valid || pointwise_smoother(h->cfg)) return false;
     h->sweep_prev_valid = false;
     const int ld = l.n_pad, nb = begin_table ? nb_list : l.ord.n_blocks();
     if (nb <= 0) return true;
@@ -283,13 +308,14 @@ bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const int* begin
 
 // true when smoothing level l from a zero iterate needs no materialised zero vector (block sweeps, at least one of them)
 inline bool smooth_from_zero_ok(gmg_handle h, const Level& l, int iters) {
-    return iters > 0 && h->cfg.smoother != GMG_SMOOTHER_JACOBI && l.ord.blocked;
+    return iters > 0 && !pointwise_smoother(h->cfg) && l.ord.blocked;
 }
 
 template <class T = double>
 void launch_smooth(gmg_handle h, Level& l, int d, int iters, bool from_zero = false) {
     if (iters <= 0) return;
     if (h->cfg.smoother == GMG_SMOOTHER_JACOBI) launch_jacobi_sweeps<T>(h, l, d, iters);
+    else if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV) launch_cheby_steps<T>(h, l, d, iters);
     else if (l.ord.blocked) launch_block_sweeps<T>(h, l, d, iters, from_zero);
     else launch_gs_sweeps<T>(h, l, d, iters);
 }
@@ -359,7 +385,7 @@ void launch_restrict(gmg_handle h, Level& fine, Level& coarse, int d, const T* s
 // which fused form the restriction into `coarse` takes: 0 none, 1 restrict_sweep0 (entry-parallel sweep), 2 gs_block4<.., FR = true> (quad layout)
 template <class T>
 int restrict_sweep0_kind(gmg_handle h, const Level& fine, const Level& coarse, int d, bool src_il) {
-    if (!h->cfg.fuse_restrict_sweep || h->cfg.smoother == GMG_SMOOTHER_JACOBI || h->cfg.pre_iters <= 0 || d > 4) return 0;
+    if (!h->cfg.fuse_restrict_sweep || pointwise_smoother(h->cfg) || h->cfg.pre_iters <= 0 || d > 4) return 0;
     if (!coarse.ord.blocked || fine.R.lpr != 4 || !(h->cfg.restrict_sigma == 0 || h->cfg.restrict_sigma == 64)) return 0;
     if (coarse.use_ep) return (coarse.n_pad == 64 * coarse.ord.n_blocks() && fine.R.n_slices == 4 * coarse.ord.n_blocks()) ? 1 : 0;      // (block b = rows 64 b .. 64 b + 63)
     // quad layout: a wave of the block sweep covers the 16 rows of one restriction slice; plain 32-bit restriction, column-major source
@@ -492,7 +518,7 @@ int ensure_vectors(gmg_handle h, int d) {
     for (auto& l : h->lv) {
         for (double** p : {&l.x, &l.b, &l.r, &l.tmp}) {
             if (*p) { (void)dev_free(*p); *p = nullptr; }
-            if (p == &l.tmp && h->cfg.smoother != GMG_SMOOTHER_JACOBI && !l.ord.blocked) continue;
+            if (p == &l.tmp && !pointwise_smoother(h->cfg) && !l.ord.blocked) continue;
             size_t bytes = sizeof(double) * (size_t)l.n_pad * d;
             HIPCHK(dev_malloc((void**)p, bytes));
             HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));
@@ -500,7 +526,7 @@ int ensure_vectors(gmg_handle h, int d) {
         for (float** p : {&l.x32, &l.b32, &l.r32, &l.tmp32}) {
             if (*p) { (void)dev_free(*p); *p = nullptr; }
             if (!h->cfg.inner_precision) continue;
-            if (p == &l.tmp32 && h->cfg.smoother != GMG_SMOOTHER_JACOBI && !l.ord.blocked) continue;
+            if (p == &l.tmp32 && !pointwise_smoother(h->cfg) && !l.ord.blocked) continue;
             size_t bytes = sizeof(float) * (size_t)l.n_pad * d;
             HIPCHK(dev_malloc((void**)p, bytes));
             HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));
@@ -754,7 +780,7 @@ void enqueue_up(gmg_handle h, int d, int k0 = 0) {
         const T* src = il ? Prec<T>::r(h->lv[k + 1]) : Prec<T>::x(h->lv[k + 1]);
         launch_prolong_add<T>(h, l, h->lv[k + 1], d, src, Prec<T>::x(l), il);     // :1082
         constexpr bool no_il = false;
-        if (k == 1 && k0 == 0 && d > 1 && d <= 4 && !no_il && h->cfg.post_iters > 0 && l.ord.blocked && l.use_ep && h->cfg.smoother != GMG_SMOOTHER_JACOBI)
+        if (k == 1 && k0 == 0 && d > 1 && d <= 4 && !no_il && h->cfg.post_iters > 0 && l.ord.blocked && l.use_ep && !pointwise_smoother(h->cfg))
             h->il_sweep_out = (void*)Prec<T>::r(l);
         launch_smooth<T>(h, l, d, h->cfg.post_iters);                                                // :1085
         h->il_sweep_out = nullptr;

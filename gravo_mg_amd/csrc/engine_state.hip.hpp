@@ -119,6 +119,7 @@ struct Level {
     DevCsr dA;                    // natural numbering, device copy: RAP input, layout source, source of the lazy host copy
     DevSell Aoff;                 // off-diagonal part, device numbering
     double* diag = nullptr;       // n_pad
+    double cheby_lambda = 0.0;    // GMG_SMOOTHER_CHEBYSHEV: Gershgorin bound of D^-1 A_k (finish_system -> compute_cheby_bounds); 0 = not computed
     DevSell P, R;                 // U_k (rows: this level) and U_k^T (rows: next level); unused on level L
     // blocked levels (block-hybrid Gauss-Seidel): in-block part (16-bit local columns) + off-block part
     DevSell Ain, Aout;
@@ -190,6 +191,7 @@ enum class LiveSystem { none, placeholder, system };
 struct gmg_solver_s {
     DevPool pool;
     DistP2P* p2p = nullptr;              // engine-driven multi-GPU cycle (engine_dist.hip.hpp)
+    double dbg_cheby_ratio = 0.0;        // gmg_debug_set("cheby_ratio"): this handle's interval ratio instead of the process-wide one (scripts/cheby_cycles.py scans it); 0 = none
     int dbg_col16_uncovered = 0;         // gmg_debug_set("col16_uncovered"): set-up fault injection of the tests (gravomg_hip_internal.h)
     gmg_config cfg;
     std::string err;
@@ -635,6 +637,20 @@ constexpr int kQuadLevelRows = 65536;
 constexpr int kEpMaxBlockEntries = 6144;        // largest explicit chunk of a block the unpadded sweep keeps in LDS (48 KB of fp64 products)
 constexpr int kEpMaxBlockLower = 3584;          // ... and largest lower chunk (staged as 16-byte records: 56 KB; the launch stays below the 64 KB of dynamic LDS)
 constexpr int kBcsrMaxBlockEntries = 4096;      // largest block the block-CSR sweep stages in LDS (48 KB of fp64 entries)
+// Smoothers whose step is one pass x_out = f(x_in) over all rows (weighted Jacobi, Chebyshev) and not a Gauss-Seidel sweep: no colour or block
+// order, ping-pong between x and tmp, no sweep-derived residual, no fused first sweep, no interleaved sweep output, a materialised zero guess.
+inline bool pointwise_smoother(const gmg_config& c) { return c.smoother == GMG_SMOOTHER_JACOBI || c.smoother == GMG_SMOOTHER_CHEBYSHEV; }
+inline const char* smoother_name(const gmg_config& c) {
+    return c.smoother == GMG_SMOOTHER_JACOBI ? "GMG_SMOOTHER_JACOBI" : (c.smoother == GMG_SMOOTHER_CHEBYSHEV ? "GMG_SMOOTHER_CHEBYSHEV" : "GMG_SMOOTHER_MULTICOLOR_GS");
+}
+// lambda_max / lambda_min of the Chebyshev smoother's interval: GMG_CHEBY_RATIO (read once per process) over the compiled default; a
+// measurement script may give one handle its own (gmg_debug_set "cheby_ratio")
+inline double cheby_ratio(gmg_handle h) {
+    if (cheby_ratio_usable(h->dbg_cheby_ratio)) return h->dbg_cheby_ratio;
+    const double env = EnvSwitches::get().cheby_ratio;
+    return cheby_ratio_usable(env) ? env : kChebyRatio;
+}
+
 inline bool wants_block_csr(gmg_handle h, int lpr) { return h->cfg.block_csr != 0 && lpr == 1 && h->cfg.block_rows == 64; }
 inline bool wants_block_ep(gmg_handle h, int lpr) { return h->cfg.block_ep != 0 && lpr == 1 && h->cfg.block_rows == 64; }
 

@@ -204,6 +204,43 @@ std::future<bool> spawn_coarse_factor(gmg_handle h, bool same_pattern, double* m
     });
 }
 
+// GMG_SMOOTHER_CHEBYSHEV: the Gershgorin bound of D^-1 A_k of every smoothed level from the arrays the smoother reads (gmgs::gershgorin_rows +
+// its reduction), one double per level, all of them read back with one copy.  Timing keys "cheby_lambda_l<k>" and "cheby_ratio".  The
+// coefficients of the steps are kernel arguments: captured graphs hold the old ones, so a bound that moved drops them.
+int compute_cheby_bounds(gmg_handle h) {
+    const int L = h->L;
+    constexpr int per_block = gmgs::kGershBlock / 64;
+    int max_blocks = 1;
+    for (int k = 0; k < L; ++k) {
+        if (h->lv[k].Aoff.lpr != 1 || !h->lv[k].Aoff.slice_ptr || !h->lv[k].diag) return fail(h, GMG_ERR_STATE, "the Chebyshev smoother needs the one-lane-per-row operator layout of every level");
+        max_blocks = std::max(max_blocks, (h->lv[k].Aoff.n_slices + per_block - 1) / per_block);
+    }
+    DevTmp<double> partials, bounds;
+    int rc;
+    if ((rc = partials.alloc(h, (size_t)max_blocks)) || (rc = bounds.alloc(h, (size_t)L))) return rc;
+    for (int k = 0; k < L; ++k) {
+        const Level& l = h->lv[k];
+        const int nblk = (l.Aoff.n_slices + per_block - 1) / per_block;
+        if (nblk > 0) hipLaunchKernelGGL(gmgs::gershgorin_rows<double>, dim3(nblk), dim3(gmgs::kGershBlock), 0, h->stream, l.Aoff.slice_ptr, (const double*)l.Aoff.val,
+                                         (const double*)l.diag, l.Aoff.n_slices, partials.p);
+        hipLaunchKernelGGL(gmgs::gershgorin_reduce, dim3(1), dim3(gmgs::kGershBlock), 0, h->stream, (const double*)partials.p, nblk, bounds.p + k);
+    }
+    std::vector<double> host((size_t)L, 0.0);
+    HIPCHK(hipMemcpyAsync(host.data(), bounds.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (auto it = h->timing.begin(); it != h->timing.end();) it = it->first.rfind("cheby_lambda_l", 0) == 0 ? h->timing.erase(it) : std::next(it);      // (levels of an earlier hierarchy)
+    bool moved = false;
+    for (int k = 0; k < L; ++k) {
+        if (!(host[k] >= 1.0) || !std::isfinite(host[k])) return fail(h, GMG_ERR_NUMERIC, "the Gershgorin bound of level " + std::to_string(k) + " is not finite");
+        moved = moved || host[k] != h->lv[k].cheby_lambda;
+        h->lv[k].cheby_lambda = host[k];
+        h->timing["cheby_lambda_l" + std::to_string(k)] = host[k];
+    }
+    h->timing["cheby_ratio"] = cheby_ratio(h);
+    if (moved) drop_graphs(h);
+    return GMG_OK;
+}
+
 // The end of every set-up: where the coarsest solve runs (+ its dense inverse unless inverse_ready), the fp32 twins, the mass -- when it
 // changed or has no device copy (after the drop_system of a full set-up: always), and not for placeholder values.
 int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, bool alloc_twins, bool placeholder) {
@@ -213,6 +250,7 @@ int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, boo
     h->coarse_device = want_coarse_device(h, h->lv[L].A.n_outer);
     h->timing["coarse_on_device"] = h->coarse_device ? 1.0 : 0.0;
     if (h->coarse_device && !inverse_ready && (rc = build_coarse_inverse_device(h))) return rc;
+    if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV && !placeholder && (rc = compute_cheby_bounds(h))) return rc;      // (the real values bring the bounds: no keys before a gmg_set_system)
     if (h->cfg.inner_precision && (rc = refresh_fp32_twins(h, alloc_twins))) return rc;
     if (!placeholder && !h->mass.empty() && (h->mass_dirty || !h->d_mass)) {
         if ((int)h->mass.size() != n) return fail(h, GMG_ERR_INVALID, "mass size does not match the system");
@@ -469,7 +507,7 @@ public:
     }
     int run() {
         h->timing["setup_wait_ordering"] = 0.0; h->timing["setup_device_layout"] = 0.0;
-        if (part && !(device_setup && h->cfg.device_rap && mc)) return fail(h, GMG_ERR_UNSUPPORTED, "a partitioned set-up needs device_setup = 1, device_rap = 1 and the multicolour smoother");
+        if (part && !(device_setup && h->cfg.device_rap && mc)) return fail(h, GMG_ERR_UNSUPPORTED, std::string("a partitioned set-up needs device_setup = 1, device_rap = 1 and the multicolour smoother (this handle runs ") + smoother_name(h->cfg) + ")");
         h->partitioned = false;
         h->pool.reset_peak();
         int rc;

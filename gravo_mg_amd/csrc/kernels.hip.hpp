@@ -1112,6 +1112,37 @@ __global__ __launch_bounds__(kBlock) void jacobi_sweep(const int64_t* __restrict
     }
 }
 
+// One step of the Chebyshev smoother (GMG_SMOOTHER_CHEBYSHEV; cheby_coeffs.hpp has the recurrence and where c1 / c2 come from):
+//   z = (b - A x_in) / diag,   p <- c1 p + c2 z  (FIRST: p <- c2 z, p is not read),   x_out = x_in + p.
+// One wave per 64-row slice, lane = row (the levels of a pointwise smoother are never blocked: one lane per row); level 0 reads its 16-bit
+// column codes / uniform slices like its SpMV (C16, row_dot_sel).  x ping-pongs like the Jacobi sweep's; p belongs to the row's own lane and is
+// updated in place.  No atomics, no order between rows: the same input gives the same bits.
+template <class T, int D, bool FIRST, int C16 = 0>
+__global__ __launch_bounds__(kBlock) void cheby_step(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
+                                                     const T* __restrict__ val, const T* __restrict__ diag,
+                                                     const T* __restrict__ b, const T* __restrict__ x_in,
+                                                     T* __restrict__ x_out, T* __restrict__ p, int ld, int n_slices, T c1, T c2,
+                                                     int xcd_swizzle, const unsigned* __restrict__ col16 = nullptr,
+                                                     const int* __restrict__ win_base = nullptr, int c16_arg = 0) {
+    const int s = wave_slice(n_slices, xcd_swizzle);
+    if (s >= n_slices) return;
+    const int lane = threadIdx.x & 63;
+    const int row = s * 64 + lane;
+    T acc[D];
+    row_dot_sel<T, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x_in, ld, s, lane, acc);
+    const T dg = diag[row];
+#pragma unroll
+    for (int c = 0; c < D; ++c) {
+        const int64_t i = row + (int64_t)c * ld;
+        const T xi = x_in[i];
+        const T z = (b[i] - row_ax(acc[c], dg, xi)) / dg;
+        T pn = c2 * z;
+        if constexpr (!FIRST) pn = c1 * p[i] + pn;
+        p[i] = pn;
+        x_out[i] = xi + pn;
+    }
+}
+
 // MODE 0: y = A x      MODE 1: y = b - A x   (gravomg/src/multigrid_solver.cpp:1066)
 // LPR = lanes per row of the SELL layout (1, or 4 on the coarse levels): slices then hold 64 / LPR rows.
 template <class T, int D, int MODE, int LPR, int C16 = 0, int YI = 0>

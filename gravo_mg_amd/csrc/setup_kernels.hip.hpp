@@ -976,4 +976,54 @@ __global__ __launch_bounds__(256) void permute_symmetric_scatter(const double* _
     for (int c = threadIdx.x; c < n; c += 256) dst[perm[c]] = src[c];
 }
 
+// ---- Gershgorin bound of D^-1 A (the Chebyshev smoother's lambda_max, cheby_coeffs.hpp) --------------------------------------------------
+// max_i sum_j |a_ij| / |a_ii| with the diagonal term included, over the arrays the smoother itself reads: the off-diagonal SELL (one lane
+// per row) and the diagonal.  One wave per 64-row slice: a row's 1 + sum |val| / |diag|, the wave's maximum by shuffles, the block's through
+// LDS into partials[block]; gershgorin_reduce (one block) then takes the maximum of the partials.  Padding entries hold 0 and padding rows
+// an empty row with a unit diagonal: they contribute exactly 1, which no real row falls below.  A maximum does not depend on the order.
+constexpr int kGershBlock = 256;
+template <class T>
+__global__ __launch_bounds__(kGershBlock) void gershgorin_rows(const int64_t* __restrict__ slice_ptr, const T* __restrict__ val, const T* __restrict__ diag,
+                                                               int n_slices, double* __restrict__ partials) {
+    __shared__ double red[kGershBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * (kGershBlock / 64) + wave;
+    double v = 1.0;
+    if (s < n_slices) {
+        const int64_t p0 = slice_ptr[s];
+        const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
+        const T* vp = val + p0 + lane;
+        double sum = 0.0;
+        for (int j = 0; j < w; ++j) sum += fabs((double)vp[(int64_t)j * 64]);
+        v = 1.0 + sum / fabs((double)diag[(int64_t)s * 64 + lane]);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < kGershBlock / 64; ++w2) m = fmax(m, red[w2]);
+        partials[blockIdx.x] = m;
+    }
+}
+
+__global__ __launch_bounds__(kGershBlock) void gershgorin_reduce(const double* __restrict__ partials, int n, double* __restrict__ out) {
+    __shared__ double red[kGershBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double v = 1.0;
+    for (int i = threadIdx.x; i < n; i += kGershBlock) v = fmax(v, partials[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < kGershBlock / 64; ++w2) m = fmax(m, red[w2]);
+        *out = m;
+    }
+}
+
 }  // namespace gmgs

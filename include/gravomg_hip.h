@@ -44,7 +44,7 @@ typedef enum {
     GMG_DIVERGED = 1           /* gmg_solve only, NOT an error: the iteration did not contract (see gmg_solve); x holds the last iterate */
 } gmg_status;
 
-enum { GMG_SMOOTHER_MULTICOLOR_GS = 0, GMG_SMOOTHER_JACOBI = 1 };
+enum { GMG_SMOOTHER_MULTICOLOR_GS = 0, GMG_SMOOTHER_JACOBI = 1, GMG_SMOOTHER_CHEBYSHEV = 2 };
 /* where the coarsest direct solve (multigrid_solver.cpp:1075) is applied.  HOST_LDLT: back-substitution with the host's supernodal factor, one
  * device -> host -> device round trip per cycle.  DEVICE_INVERSE: one dense symmetric matrix-vector product with A_L^-1 on the device; the inverse
  * is built on the device from the host's factor at gmg_set_system (timing keys "coarse_inverse_ms").  AUTO (default): DEVICE_INVERSE while the
@@ -53,7 +53,16 @@ enum { GMG_COARSE_HOST_LDLT = 0, GMG_COARSE_DEVICE_INVERSE = 1, GMG_COARSE_AUTO 
 
 typedef struct {
     int device;            /* HIP device ordinal */
-    int smoother;          /* GMG_SMOOTHER_*: multicolour Gauss-Seidel (default) or weighted Jacobi */
+    int smoother;          /* GMG_SMOOTHER_*: multicolour Gauss-Seidel (default), weighted Jacobi or a Chebyshev polynomial; any other value: gmg_create
+                            * returns GMG_ERR_INVALID.  GMG_SMOOTHER_CHEBYSHEV: Chebyshev iteration on D^-1 A over [lambda / ratio, lambda], lambda the
+                            * Gershgorin bound max_i sum_j |a_ij| / |a_ii| of the level (computed at every gmg_set_system / values refresh; timing keys
+                            * "cheby_lambda_l<k>" and "cheby_ratio", absent with the other smoothers).  pre_iters / post_iters are then the polynomial
+                            * DEGREES: that many steps, each one pass over the operator in one launch, every gmg_smooth / smoothing leg starting a new
+                            * polynomial.  It converges for every symmetric positive definite system, its iterates do not depend on any ordering, and a
+                            * cycle with pre_iters == post_iters is a symmetric operator.  gs_omega, jacobi_omega, block_* and fuse_restrict_sweep are
+                            * without effect, speculate_head too (it needs the multicolour smoother); like Jacobi it runs on one device only (the
+                            * multi-rank entry points refuse the handle).  accelerate, inner_precision, use_graph, gmg_solve_device and the values-only
+                            * refresh work as with the other smoothers. */
     double jacobi_omega;   /* damping for GMG_SMOOTHER_JACOBI (default 0.67) */
     int pre_iters;         /* MultigridSolver::preIters  (gravomg_bindings/src/cpp/core.cpp:55) */
     int post_iters;        /* MultigridSolver::postIters (core.cpp:56) */

@@ -20,7 +20,9 @@ int gmg_debug_sell_copy(gmg_handle h, int k, int which, int64_t* slice_ptr, int*
 
 /* Set-up fault injection for the tests, per handle, effective from the next gmg_set_system.  Keys:
  *   "col16_uncovered" = N > 0: every N-th level-0 slice is treated as not covered by its column windows (flagged one by one, c16 mode 2);
- *                       N < 0: the first -N slices (a prefix, c16 mode 1); 0: off.  Results must not change (tests/test_gpu_setup.py). */
+ *                       N < 0: the first -N slices (a prefix, c16 mode 1); 0: off.  Results must not change (tests/test_gpu_setup.py).
+ *   "cheby_ratio" = R > 1: this handle's Chebyshev smoother runs over [lambda / R, lambda] instead of the process-wide ratio (GMG_CHEBY_RATIO /
+ *                       the compiled default), effective from the next smoothing step; 0: off.  Measurement only (scripts/cheby_cycles.py). */
 int gmg_debug_set(gmg_handle h, const char* key, double value);
 
 /* The per-point parent selection of ONE hierarchy level (multigrid_solver.cpp:291-452) on job arrays the caller builds by hand, in the layout of
