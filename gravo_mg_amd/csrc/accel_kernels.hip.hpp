@@ -205,14 +205,16 @@ __global__ __launch_bounds__(kReduceBlock) void accel_reduce_beta(const double* 
 
 // alpha[c], guarded[c] (accel_step) from the partials of accel_orth; s_store (may be null: depth 1) receives what the ring keeps as s_j of
 // the direction just formed; *guard_steps counts the guarded (iteration, column) steps of the solve (one block, launches in stream order: a plain add)
+// bb[c] = <b, b> of the column for the floor guard (gmg::accel_floor; 0 in the first iteration of a solve: not known yet, accel_reduce_bb)
 __global__ __launch_bounds__(kReduceBlock) void accel_reduce_alpha(const double* __restrict__ partials, int n_blocks, int dc, double* __restrict__ alpha,
-                                                                   double* __restrict__ guarded, double* __restrict__ s_store, double* __restrict__ guard_steps) {
+                                                                   double* __restrict__ guarded, double* __restrict__ s_store, double* __restrict__ guard_steps,
+                                                                   const double* __restrict__ bb) {
     __shared__ double tot[kAccelMaxComp];
     __shared__ int flag[4];
     accel_block_total(partials, n_blocks, 2 * dc, tot);
     const int c = threadIdx.x;
     if (c < dc) {
-        const gmg::AccelStep st = gmg::accel_step(tot[2 * c], tot[2 * c + 1]);
+        const gmg::AccelStep st = gmg::accel_step(tot[2 * c], tot[2 * c + 1], gmg::accel_floor(bb[c]));
         alpha[c] = st.alpha;
         guarded[c] = st.guarded ? 1.0 : 0.0;
         if (s_store) s_store[c] = st.s_store;
@@ -224,6 +226,13 @@ __global__ __launch_bounds__(kReduceBlock) void accel_reduce_alpha(const double*
         for (int k = 0; k < dc; ++k) n += flag[k];
         if (n) *guard_steps += (double)n;
     }
+}
+
+// bb[c] = <b, b> of column c from the partials of accel_update ([2 c + 1]: the check's sums of w b^2), once per solve after its first update
+__global__ __launch_bounds__(kReduceBlock) void accel_reduce_bb(const double* __restrict__ partials, int n_blocks, int dc, double* __restrict__ bb) {
+    __shared__ double tot[kAccelMaxComp];
+    accel_block_total(partials, n_blocks, 2 * dc, tot);
+    if ((int)threadIdx.x < dc) bb[threadIdx.x] = tot[2 * threadIdx.x + 1];
 }
 
 }  // namespace gmgk

@@ -707,17 +707,20 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     const int accel = h->cfg.accelerate;
     int confirmations = 0;
     Level& l0 = h->lv[0];
-    auto accel_step = [&](const SolveRule& rule, double& residue, int&) -> int {
+    auto accel_step = [&](SolveRule& rule, double& residue, int&) -> int {
         if ((rc = vcycle_resident(h, d, -1))) return rc;
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, l0.r);                  // r~ = b - A x~ (q = r - r~ = A z: no product of its own)
         if ((rc = launch_accel_step(h, d, stop_type, rule.cycles))) return rc;
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
         if (rule_goes_on(rule_after(rule, residue))) return GMG_OK;
+        const double recurrence = residue;
         if ((rc = launch_norm(h, d, stop_type))) return rc;                   // it would end the loop: the check on the iterate itself decides
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
         ++confirmations;
+        // (a recurrence that ran on below the accuracy floor is not what the verdict measures this residue against: solve_rule.hpp)
+        rule = rule_confirmed(rule, recurrence, residue, rule_floor(h->h_norm, d, stop_type));
         // (confirmed, above the tolerance and the loop will go on: the recurrence restarts from the residual of the iterate, the directions stay)
         if (rule_goes_on(rule_after(rule, residue))) launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
         return GMG_OK;
@@ -741,7 +744,7 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     int verdict;
     if (accel > 0) {
         if ((rc = ensure_accel(h))) return rc;
-        HIPCHK(hipMemsetAsync(h->accel.scal, 0, sizeof(double) * ((size_t)8 * h->accel.d + 1), h->stream));      // nothing stored (s_j = 0), no guarded step
+        HIPCHK(hipMemsetAsync(h->accel.scal, 0, sizeof(double) * ((size_t)9 * h->accel.d + 1), h->stream));      // nothing stored (s_j = 0), no guarded step, <b, b> not known
         HIPCHK(hipMemcpyAsync(h->accel.xk, l0.x, sizeof(double) * (size_t)l0.n_pad * d, hipMemcpyDeviceToDevice, h->stream));
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, accel_step);

@@ -1072,7 +1072,7 @@ int ensure_accel(gmg_handle h) {
     int rc;
     for (double** p : {&a.xk, &a.r, &a.z0}) if ((rc = vec(p))) return rc;
     for (int j = 0; j < m - 1; ++j) for (double** p : {&a.zs[j], &a.qs[j]}) if ((rc = vec(p))) return rc;
-    HIPCHK(dev_malloc((void**)&a.scal, sizeof(double) * ((size_t)8 * D + 1)));
+    HIPCHK(dev_malloc((void**)&a.scal, sizeof(double) * ((size_t)9 * D + 1)));          // alpha, guarded, 3 betas, 3 s_j per column; guard_steps; <b, b> per column
     HIPCHK(dev_malloc((void**)&a.partials, sizeof(double) * (size_t)gmgk::kAccelMaxBlocks * gmgk::kAccelMaxComp));
     a.depth = m; a.d = D; a.n_pad = n_pad;
     return GMG_OK;
@@ -1088,7 +1088,8 @@ int launch_accel_step(gmg_handle h, int d, int type, int done) {
     const int wslot = stored > 0 ? done % stored : -1;           // ring slot the new direction replaces (the oldest, or a free one)
     const int nblk = std::max(1, std::min(gmgk::kAccelMaxBlocks, (n_pairs + gmgk::kAccelBlock - 1) / gmgk::kAccelBlock));
     const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
-    double *alpha = a.scal, *guarded = a.scal + DA, *beta = a.scal + 2 * DA, *s_slot = a.scal + 5 * DA, *guard_steps = a.scal + 8 * DA;
+    double *alpha = a.scal, *guarded = a.scal + DA, *beta = a.scal + 2 * DA, *s_slot = a.scal + 5 * DA, *guard_steps = a.scal + 8 * DA,
+           *bb = a.scal + 8 * DA + 1;
     for_col_chunks(d, [&](int c0, int dc) {
         const size_t off = (size_t)c0 * ld;
         gmgk::AccelRing ring{};
@@ -1103,9 +1104,11 @@ int launch_accel_step(gmg_handle h, int d, int type, int done) {
         DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::accel_orth<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.z0 + off, q0, a.r + off, ring, ns, zw, qw,
                                           beta + c0, DA, w, ld, n_pairs, a.partials));
         hipLaunchKernelGGL(gmgk::accel_reduce_alpha, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, alpha + c0, guarded + c0,
-                           wslot >= 0 ? s_slot + (size_t)wslot * DA + c0 : nullptr, guard_steps);
+                           wslot >= 0 ? s_slot + (size_t)wslot * DA + c0 : nullptr, guard_steps, bb + c0);
         DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::accel_update<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.xk + off, l.x + off, a.r + off,
                                           zw ? zw : a.z0 + off, qw ? qw : q0, a.z0 + off, q0, alpha + c0, guarded + c0, l.b + off, w, ld, n_pairs, a.partials));
+        // (the floor guard's <b, b>: kept from the first update's sums, zero until then)
+        if (done == 0) hipLaunchKernelGGL(gmgk::accel_reduce_bb, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, bb + c0);
         launch_reduce(h, nblk, dc, c0, c0 + 4 >= d, a.partials);
     });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));

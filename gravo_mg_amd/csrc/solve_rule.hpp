@@ -56,6 +56,26 @@ GMG_RULE_HD inline SolveRule rule_after(SolveRule r, double residue) {
     r.blown = rule_blown(residue, r.least, r.cycles);
     return r;
 }
+// The accelerated loop (gmg_config::accelerate) reports the residue of a recurrence and confirms it on the iterate where it would end the loop.
+// A confirmed residue of more than twice the recurrence's says the recurrence has lost touch with b - A x (it runs on below the accuracy floor):
+// what it reported below the confirmed value was never seen on an iterate, and is no evidence of a blow-up -- `least` rises to the confirmed
+// value.  A confirmed residue on the floor itself (at most `floor`: 1e-12 |b| in the stop type's measure, rule_floor) is measured against nothing
+// smaller: a cycle that solves the system at once leaves a first recurrence of eps^2, `first` and `least` rise to the confirmed value -- a
+// solve that ends on the floor has not diverged.  The state BEFORE rule_after(confirmed).
+GMG_RULE_HD inline SolveRule rule_confirmed(SolveRule r, double recurrence, double confirmed, double floor) {
+    if (r.cycles < 1) return r;
+    const bool lost_touch = confirmed > 2.0 * recurrence, on_floor = confirmed <= floor;
+    if ((lost_touch || on_floor) && r.least < confirmed) r.least = confirmed;
+    if (on_floor && r.first < confirmed) r.first = confirmed;
+    return r;
+}
+// 1e-12 |b| as a residue of this stop type, from the check's sums (s[2c + 1]: sum of w b^2): relative for types 0 .. 2
+GMG_RULE_HD inline double rule_floor(const double* s, int d, int type) {
+    if (type != 3) return 1e-12;
+    double t = 0.0;
+    for (int c = 0; c < d; ++c) t += s[2 * c + 1];
+    return 1e-12 * __builtin_sqrt(t);
+}
 GMG_RULE_HD inline bool rule_goes_on(const SolveRule& r) { return rule_wants_more(r.residue, r.tol, r.blown) && r.cycles < r.max_iter; }
 // Not contracting: the loop ended above the tolerance with a residue that is not finite, 1e4 x the smallest seen, or larger than after the first cycle.
 GMG_RULE_HD inline bool rule_diverged(const SolveRule& r) { return !(r.residue <= r.tol) && (r.blown || (r.cycles > 1 && r.residue > r.first)); }

@@ -89,8 +89,26 @@ int main() {
     const double inf = std::numeric_limits<double>::infinity(), nan = std::numeric_limits<double>::quiet_NaN();
     const double tiny = std::numeric_limits<double>::denorm_min(), huge = std::numeric_limits<double>::max();
     static_assert(kAccelMaxDepth == 4 && kAccelMaxStored == 3, "depths");
+    // the floor guard: <q, q> at or below 1e-25 <b, b> is noise; <b, b> of 0, below 0 or NaN means "not known" -- no floor
+    static_assert(kAccelFloorRel2 == 1e-25, "the floor");
+    EXPECT(accel_floor(4.0) == kAccelFloorRel2 * 4.0 && accel_floor(0.0) == 0.0 && accel_floor(-1.0) == 0.0 && accel_floor(nan) == 0.0 && std::isinf(accel_floor(inf)));
+    AccelStep st = accel_step(accel_floor(4.0), 2e-25, accel_floor(4.0));                     // on the floor: the comparison includes it
+    EXPECT(st.guarded == 1 && st.alpha == 1.0 && st.s_store == 0.0);
+    st = accel_step(2.0 * accel_floor(4.0), 0.5 * accel_floor(4.0), accel_floor(4.0));      // above it: an ordinary step
+    EXPECT(!st.guarded && st.alpha == 0.25 && st.s_store == 2.0 * accel_floor(4.0));
+    st = accel_step(tiny, tiny, accel_floor(4.0));
+    EXPECT(st.guarded == 1 && st.s_store == 0.0);
+    st = accel_step(tiny, tiny, accel_floor(0.0));                         // no floor known (the first iteration): only the old guard
+    EXPECT(!st.guarded && st.alpha == 1.0);
+    st = accel_step(tiny, tiny, nan);                                      // a NaN floor compares false
+    EXPECT(!st.guarded);
+    st = accel_step(1.0, 1.0, accel_floor(inf));                           // <b, b> not finite: everything is below it
+    EXPECT(st.guarded == 1);
+    st = accel_step(nan, 1.0, accel_floor(4.0));
+    EXPECT(st.guarded == 1 && st.alpha == 1.0);
+    EXPECT(accel_beta(123.0, accel_step(1e-26, 1.0, accel_floor(1.0)).s_store) == 0.0);      // a direction on the floor is never divided by later
     // normal values
-    AccelStep st = accel_step(4.0, 2.0);
+    st = accel_step(4.0, 2.0);
     EXPECT(!st.guarded && st.alpha == 0.5 && st.s_store == 4.0);
     st = accel_step(4.0, -2.0);
     EXPECT(!st.guarded && st.alpha == -0.5 && st.s_store == 4.0);

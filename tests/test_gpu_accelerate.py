@@ -1,6 +1,6 @@
 """gmg_config::accelerate on a real device: the solve loop with truncated GCR around the V-cycle (engine.hip::solve_common, accel_kernels.hip.hpp).
 
-The reference is a numpy restatement of the recombination (`_model`), written here: its cycle is `vcycle(b, x)` of a SECOND handle created with
+The reference is a numpy restatement of the recombination (tests/accelerate_model.py): its cycle is `vcycle(b, x)` of a SECOND handle created with
 accelerate = 0 (existing code), its A x is scipy's, everything fp64.  The model differs from the device only in the order of its sums.
 
 Measured on an MI355X over the eighteen model-comparison cases below (eight dependent iterations each), deviations taken relative to the
@@ -27,6 +27,7 @@ import numpy as np
 import pytest
 
 from tests import problems
+from tests.accelerate_model import accelerated_loop
 
 pytestmark = pytest.mark.gpu
 
@@ -68,72 +69,10 @@ def _bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
-def _weights(P, stop_type):
-    return {0: np.ones(P.n), 1: 1.0 / P.mass, 2: P.mass, 3: np.ones(P.n)}[stop_type][:, None]
-
-
-def _norm(rr, bb, stop_type):
-    """solve_rule.hpp::norm_from_sums on the per-column sums of w r^2 and w b^2."""
-    if stop_type == 3:
-        return float(np.sqrt(rr.sum()))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        v = np.sqrt(rr) / np.sqrt(bb) if stop_type == 0 else np.sqrt(rr / bb)
-    out = v[0]
-    for t in v[1:]:
-        if t > out:
-            out = t
-    return float(out)
-
-
-def _usable(s):
-    return np.isfinite(s) & (s != 0.0)
-
-
 def _model(name, cfg, rhs, x0, m, stop_type, tol, max_iter):
-    """The accelerated loop of the issue, restated: returns (x, iterations, residues, guarded steps)."""
+    """tests/accelerate_model.accelerated_loop with the cycle of a second handle (accelerate = 0): (x, iterations, residues, guarded steps)."""
     P = _problem(name)
-    cyc = _engine(name, 0, cfg)
-    A = P.lhs.tocsr()
-    w = _weights(P, stop_type)
-    rhs = np.asarray(rhs, dtype=np.float64)
-    x = np.array(x0, dtype=np.float64, order="F")
-    r = rhs - A @ x
-    bb = (w * rhs * rhs).sum(axis=0)
-    stored, residues, guards = [], [], 0
-    it = 0
-    while True:
-        xk = x
-        xt = np.asarray(cyc.vcycle(rhs, xk)).reshape(rhs.shape)
-        rt = rhs - A @ xt
-        z0, q0 = xt - xk, r - rt
-        z, q = z0.copy(), q0.copy()
-        with np.errstate(invalid="ignore", divide="ignore"):
-            betas = [np.where(_usable(sj), (w * q0 * qj).sum(axis=0) / sj, 0.0) for (_, qj, sj) in stored]      # all from q0: classical Gram-Schmidt
-            for beta, (zj, qj, _) in zip(betas, stored):
-                on = beta != 0.0
-                z[:, on] -= beta[on] * zj[:, on]
-                q[:, on] -= beta[on] * qj[:, on]
-            s, rho = (w * q * q).sum(axis=0), (w * r * q).sum(axis=0)
-            g = ~_usable(s)
-            alpha = np.where(g, 1.0, rho / s)
-        guards += int(g.sum())
-        zu, qu = np.where(g, z0, z), np.where(g, q0, q)
-        x = xk + alpha * zu
-        r = r - alpha * qu
-        if m > 1:
-            stored.append((z, q, np.where(g, 0.0, s)))
-            stored = stored[-(m - 1):]
-        res = _norm((w * r * r).sum(axis=0), bb, stop_type)
-        it += 1
-        confirmed = not (res > tol and it < max_iter)
-        if confirmed:
-            r_true = rhs - A @ x
-            res = _norm((w * r_true * r_true).sum(axis=0), bb, stop_type)
-        residues.append(res)
-        if not (res > tol and it < max_iter):
-            return x, it, np.array(residues), guards
-        if confirmed:
-            r = r_true
+    return accelerated_loop(P.lhs, P.mass, _engine(name, 0, cfg).vcycle, rhs, x0, m, stop_type, tol, max_iter)[:4]
 
 
 def _rel(a, b):

@@ -23,6 +23,7 @@ using namespace gmg;
 // N type d s[2d]                 -> N <residue %a>
 // R tol max_iter n r[n]          -> R <stops at> <blown> <diverged> <host goes-on words> <device goes-on words> <peek commits nothing>
 // D tol first residue cycles blown -> D <diverged>
+// C tol floor n r[n] confirmed   -> C <least %a> <blown> <diverged>
 int main(int argc, char** argv) {
     if (argc != 2) return 2;
     std::FILE* f = std::fopen(argv[1], "r");
@@ -69,6 +70,16 @@ int main(int argc, char** argv) {
             rule.cycles = (int)num();
             rule.blown = num() != 0.0;
             std::printf("D %d\n", (int)rule_diverged(rule));
+        } else if (kind[0] == 'C') {
+            // the accelerated loop: recurrence residues cycle by cycle, the last one replaced by `confirmed` (rule_confirmed, then rule_after)
+            const double tol = num(), floor = num();
+            const int n = (int)num();
+            SolveRule rule = rule_begin(tol, n);
+            double rec = 0.0;
+            for (int i = 0; i < n; ++i) { rec = num(); if (i + 1 < n) rule = rule_after(rule, rec); }
+            const double confirmed = num();
+            rule = rule_after(rule_confirmed(rule, rec, confirmed, floor), confirmed);
+            std::printf("C %a %d %d\n", rule.least, (int)rule.blown, (int)rule_diverged(rule));
         } else return 5;
     }
     std::fclose(f);
@@ -211,3 +222,29 @@ def test_rule_cases_and_host_and_device_in_step(rule_exe):
         assert peek_ok == "1", line
     for (case, expected), line in zip(direct, out[len(_RULE_CASES):]):
         assert line == "D %d" % expected, (case, line)
+
+
+# (tol, the recurrence's residues, the confirmed residue of the last iterate) -> (least, blown, diverged)
+_CONFIRMED_CASES = [
+    ((1e-17, [1.0, 1e-8, 1e-16, 1e-24], 2e-16), (2e-16, 0, 0)),          # the recurrence ran on below the floor: what it reported is no smallest residue
+    ((1e-17, [1.0, 1e-8, 1e-22, 1e-30], 2e-16), (2e-16, 0, 0)),          # (1e6 x the smallest reported: blown without the correction)
+    ((1e-9, [1.0, 1e-3, 1e-6, 0.09], 0.1), (1e-6, 1, 1)),                # the recurrence agrees with the check: a real blow-up stays one
+    ((1e-9, [1e-3, 1e-5, 1e-7, 1e-9], 5.0), (5.0, 0, 1)),                # lost touch and above the first residue: diverged
+    ((1e-9, [1.0, 0.5, 0.25], 0.2), (0.2, 0, 0)),                        # confirmed below the recurrence
+    ((1e-9, [1.0, 0.5, 0.25], 0.5), (0.5, 0, 0)),                        # exactly twice: the comparison is strict, least is the smaller one anyway
+    ((1e-9, [1.0, 0.5, 0.25], _NAN), (0.5, 1, 1)),
+    ((1e-9, [1.0, 0.5, _NAN], 0.25), (0.25, 0, 0)),                      # a NaN recurrence compares false: nothing is corrected
+    ((1e-9, [0.5], 3.0), (3.0, 0, 0)),                                   # the first cycle: its residue is first and least whatever was reported
+    ((1e-17, [1e-30, 1e-31, 1e-32], 2e-16), (2e-16, 0, 0)),              # solved by the first cycle (its recurrence undershoots): on the floor, not diverged
+    ((1e-17, [1e-30, 1e-31, 1e-32], 2e-11), (2e-11, 0, 1)),              # ... but above the floor of 1e-12 it is
+    ((1e-17, [1e-13, 5e-14, 4e-14], 5e-14), (5e-14, 0, 0)),              # on the floor and in touch, below the first residue
+    ((1e-17, [1e-32, 3e-16, 3e-16, 3e-16], 3.1e-16), (3.1e-16, 0, 0)),    # the first recurrence undershot, the later ones are in touch (guarded steps)
+]
+
+
+def test_confirmed_residue_of_the_accelerated_loop(rule_exe):
+    """rule_confirmed: a confirmed residue of more than twice the recurrence's raises `least` to itself (never lowers it), then rule_after."""
+    out = _run(rule_exe, ["C %s %s %d %s %s" % (_hex(tol), _hex(1e-12), len(seq), " ".join(_hex(v) for v in seq), _hex(conf)) for (tol, seq, conf), _ in _CONFIRMED_CASES])
+    for ((tol, seq, conf), (least, blown, diverged)), line in zip(_CONFIRMED_CASES, out):
+        kind, got, b, dv = line.split()
+        assert kind == "C" and float.fromhex(got) == least and (int(b), int(dv)) == (blown, diverged), (seq, conf, line)
