@@ -448,13 +448,12 @@ int gmg_smooth_residual(gmg_handle h, int k, const double* b, double* x, int d, 
     if ((rc = ensure_vectors(h, d))) return rc;
     Level& l = h->lv[k];
     if ((rc = to_device(h, k, b, d, l.b))) return rc;
-    const bool zero = from_zero != 0 && k > 0 && smooth_from_zero_ok(h, l, iters);
+    SmoothAsk<double> ask;                         // (a single level's sweeps: nothing ran ahead of them, nothing rides on them)
+    ask.from_zero = from_zero != 0 && k > 0 && smooth_from_zero_ok(h, l, iters);
     if (from_zero) HIPCHK(hipMemsetAsync(l.x, 0, sizeof(double) * (size_t)l.n_pad * d, h->stream));
     else if ((rc = to_device(h, k, x, d, l.x))) return rc;
-    h->sweep_prev_valid = false;
-    h->first_sweep_fused = false;                  // (a single level's sweeps: nothing ran ahead of them)
-    launch_smooth<double>(h, l, d, iters, zero);
-    const bool delta = k > 0 && launch_residual_delta<double>(h, l, d, l.r);        // exactly what enqueue_down does
+    const SmoothDone<double> swept = launch_smooth<double>(h, l, d, iters, ask);
+    const bool delta = k > 0 && launch_residual_delta<double>(h, l, d, l.r, swept);        // exactly what enqueue_down does
     if (!delta) launch_spmv<double>(h, l, d, 1, l.b, l.x, l.r);
     h->timing["residual_from_sweep"] = delta ? 1.0 : 0.0;
     h->loaded_d = 0;
@@ -595,18 +594,13 @@ int gmg_load_problem(gmg_handle h, const double* b, const double* x0, int d) try
 } GMG_CATCH_H
 
 namespace {
-// arms the device-side decision of the residual checks enqueued inside its scope (launch_reduce) and clears it, with a head that was not
-// taken up, on every way out
-struct WatchScope {
-    gmg_handle h; bool on;
-    WatchScope(gmg_handle h_, bool on_, int mode, double tol, int type) : h(h_), on(on_) {
-        h->head_enqueued = false;
-        if (!on) return;
-        h->timing["heads_enqueued"] += 0.0; h->timing["head_decision_differs"] += 0.0;
-        h->watch_active = true; h->watch_mode = mode; h->watch_tol = tol; h->watch_type = type; h->watch_cycles_done = 0;
-    }
-    ~WatchScope() { h->watch_active = false; h->head_enqueued = false; }
-};
+// does a loop over cycles enqueue heads (head_eligible, where the loop wants them)?  Its two timing keys exist from then on.  Such a loop hands
+// every cycle a CycleWatch and whether the cycle's head is in the stream: its own locals, so nothing of them outlives it.
+inline bool loop_enqueues_heads(gmg_handle h, int d, bool wanted) {
+    if (!wanted || !head_eligible(h, d)) return false;
+    h->timing["heads_enqueued"] += 0.0; h->timing["head_decision_differs"] += 0.0;
+    return true;
+}
 }  // namespace
 
 int gmg_run_cycles(gmg_handle h, int n_cycles, int stop_type, double* residues) try {
@@ -620,12 +614,14 @@ int gmg_run_cycles(gmg_handle h, int n_cycles, int stop_type, double* residues) 
     HelperScope helper_scope(h, d);
     // (a fixed number of cycles: the first colour launch of the next one goes into the stream before the host has seen this one's norm,
     // as in the solve loop -- there the check's reduction decides on the device whether that launch does anything, solve_common)
-    WatchScope watch(h, stop_type >= 0 && head_eligible(h, d), 0, 0.0, stop_type);
+    const bool heads = loop_enqueues_heads(h, d, stop_type >= 0);
+    CycleWatch watch{0, 0.0, stop_type, 0};
+    bool head_done = false;          // this cycle's first colour launch is in the stream
     for (int i = 0; i < n_cycles; ++i) {
-        h->watch_cycles_done = i + 1;
-        if ((rc = vcycle_resident(h, d, stop_type))) return rc;
+        watch.cycles_done = i + 1;
+        if ((rc = vcycle_resident(h, d, stop_type, head_done, heads ? &watch : nullptr))) return rc;
         if (stop_type >= 0) {
-            if (watch.on && i + 1 < n_cycles) enqueue_head(h, d);
+            head_done = heads && i + 1 < n_cycles && enqueue_head(h, d);
             if ((rc = wait_norm(h))) return rc;
             if (residues) residues[i] = norm_from_sums(h->h_norm, d, stop_type);
         }
@@ -729,16 +725,18 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     // functions: gmgk::reduce_partials / SolveWatch, solve_rule.hpp) and the first colour launch of the next cycle is enqueued behind it at
     // once -- it returns without touching x when the iteration has stopped.  The ~6 us the host needs to see the norm and to get a launch to
     // the device are hidden behind that launch.  The loop follows the device's word.
-    WatchScope watch(h, accel == 0 && head_eligible(h, d), 1, tol, stop_type);
+    const bool heads = loop_enqueues_heads(h, d, accel == 0);
+    CycleWatch watch{1, tol, stop_type, 0};
+    bool head_done = false;          // the coming cycle's first colour launch is in the stream (and found the word set)
     auto plain_step = [&](const SolveRule& rule, double& residue, int& device_go) -> int {
-        h->watch_cycles_done = rule.cycles + 1;
-        const bool head = watch.on && rule.cycles + 2 <= rule.max_iter;          // (a cycle after this one is allowed)
-        if ((rc = vcycle_resident(h, d, stop_type))) return rc;
-        if (head) enqueue_head(h, d);
+        watch.cycles_done = rule.cycles + 1;
+        const bool head = heads && rule.cycles + 2 <= rule.max_iter;          // (a cycle after this one is allowed)
+        if ((rc = vcycle_resident(h, d, stop_type, head_done, heads ? &watch : nullptr))) return rc;
+        head_done = head && enqueue_head(h, d);
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
         if (head) device_go = __atomic_load_n(h->h_flag + 1, __ATOMIC_ACQUIRE) != 0;
-        if (device_go == 0) h->head_enqueued = false;                  // that launch found the word cleared and returned
+        if (device_go == 0) head_done = false;                  // that launch found the word cleared and returned
         return GMG_OK;
     };
     int verdict;
@@ -959,9 +957,8 @@ static int dist_coarse_cycle_enqueue(gmg_handle h) {
     int rc = dist_ready(h);
     if (rc) return rc;
     const int d = h->loaded_d;
-    h->first_sweep_fused = false;
-    restrict_into<double>(h, 0, d, false);          // (+ level 1's first sweep where the layouts allow it)
-    enqueue_down<double>(h, d, 1);
+    const bool first_done = restrict_into<double>(h, 0, d, false);          // (+ level 1's first sweep where the layouts allow it)
+    enqueue_down<double>(h, d, 1, first_done);
     if (h->coarse_device) enqueue_coarse_device<double>(h, d);
     else if ((rc = coarse_host_begin<double>(h, d))) return rc;
     enqueue_up<double>(h, d, 1);

@@ -63,37 +63,56 @@ template <> struct Prec<float> {
     static float* tmp(Level& l) { return l.tmp32; }
 };
 
-// The last colour launch of the cycle's last level-0 sweep also forms its rows' share of the residual check (gs_color_norm) when
-// the cycle being enqueued ends with one (h->fuse_norm_type, set by vcycle_legs): fp64, one group of <= 4 columns, >= 2 colours.
-// Its partial sums go behind the ones the norm kernel will write for the rows of the other colours (launch_norm).
+// What the launches around a level's smoothing hand to one another travels as values: a request goes down with launch_smooth, a result comes back
+// (empty where the smoother cannot serve a part of the request -- Jacobi and Chebyshev serve none: the caller then enqueues the ordinary launch).
 template <class T>
-bool fold_norm(gmg_handle, Level&, int, bool, int, int) { return false; }
+struct SmoothAsk {
+    bool from_zero = false;       // the iterate is the zero vector: the first block sweep takes no input (and the caller skipped the memset)
+    bool first_done = false;      // ... and the restriction's launch already ran that sweep: its result is in tmp (restrict_into)
+    bool head_done = false;       // level 0: the first colour launch is already in the stream (enqueue_head)
+    T* res_out = nullptr;         // level-0 pre-smoothing: where the last colour launch may write the residual of its rows (fold_residual) ...
+    bool res_il = false;          // ... as an interleaved multi-vector
+    int norm_type = -1;           // level-0 post-smoothing: the residual check the cycle ends with, which the last colour launch may join (fold_norm)
+    T* il_out = nullptr;          // level-1 post-smoothing: where the last block sweep may write an interleaved copy of the level's x
+};
+template <class T>
+struct SmoothDone {
+    int res_from = 0;             // first slice whose residual the last colour launch wrote (0: it wrote none)
+    int norm_blocks = 0;          // partial-sum blocks of the residual check the last colour launch produced (0: none)
+    const T* prev = nullptr;      // the iterate the last block sweep started from (nullptr: the zero vector) ...
+    bool prev_valid = false;      // ... where launch_residual_delta may use it
+    bool il_written = false;      // the interleaved copy asked for is in il_out
+};
+
+// The last colour launch of the cycle's last level-0 sweep also forms its rows' share of the residual check (gs_color_norm) when the cycle being
+// enqueued ends with one (type >= 0: SmoothAsk::norm_type): fp64, one group of <= 4 columns, >= 2 colours.  Its partial sums go behind the ones
+// the norm kernel will write for the rows of the other colours (launch_norm).  Returns their number of blocks, 0 where the launch is not folded.
+template <class T>
+int fold_norm(gmg_handle, Level&, int, bool, int, int, int) { return 0; }
 template <>
-bool fold_norm<double>(gmg_handle h, Level& l, int d, bool last_launch, int sb, int se) {
-    if (!last_launch || h->fuse_norm_type < 0 || &l != &h->lv[0] || d > 4 || l.ord.n_colors < 2 || se != l.Aoff.n_slices) return false;
-    const int type = h->fuse_norm_type;
+int fold_norm<double>(gmg_handle h, Level& l, int d, bool last_launch, int sb, int se, int type) {
+    if (!last_launch || type < 0 || &l != &h->lv[0] || d > 4 || l.ord.n_colors < 2 || se != l.Aoff.n_slices) return 0;
     const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
     const int nblk = grid_for(se - sb), first = norm_grid(sb);
-    if ((size_t)(first + nblk) > (size_t)h->partial_blocks) return false;
+    if ((size_t)(first + nblk) > (size_t)h->partial_blocks) return 0;
     DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_norm<D, C16>), dim3(nblk), dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr,
                                      l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, l.n_pad, sb, se, h->cfg.gs_omega, w, h->d_partials + (size_t)first * 2 * d,
                                      l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-    h->fuse_norm_blocks = nblk;
-    return true;
+    return nblk;
 }
 
-// ... and the last colour launch of the level-0 PRE-smoothing writes the residual of its rows (gs_color_residual) when the way
-// down asks for it (h->fuse_res_out, set by enqueue_down); launch_spmv then covers the slices in front of that colour only.
+// ... and the last colour launch of the level-0 PRE-smoothing writes the residual of its rows to `out` (gs_color_residual) when the way down
+// asks for it (SmoothAsk::res_out, res_il); launch_spmv then covers the slices in front of that colour only.  Returns the first slice the
+// launch covered, 0 where it is not folded.
 template <class T>
-bool fold_residual(gmg_handle, Level&, int, bool, int, int) { return false; }
+int fold_residual(gmg_handle, Level&, int, bool, int, int, T*, bool) { return 0; }
 template <>
-bool fold_residual<double>(gmg_handle h, Level& l, int d, bool last_launch, int sb, int se) {
-    if (!last_launch || !h->fuse_res_out || &l != &h->lv[0] || d > 4 || l.ord.n_colors < 2 || se != l.Aoff.n_slices || sb <= 0) return false;
-    DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), DISPATCH_FLAG(YI, h->il_r0, hipLaunchKernelGGL((gmgk::gs_color_residual<D, C16, (YI && D > 1)>), dim3(grid_for(se - sb)),
-                                     dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, h->fuse_res_out, l.n_pad, sb, se,
+int fold_residual<double>(gmg_handle h, Level& l, int d, bool last_launch, int sb, int se, double* out, bool il) {
+    if (!last_launch || !out || &l != &h->lv[0] || d > 4 || l.ord.n_colors < 2 || se != l.Aoff.n_slices || sb <= 0) return 0;
+    DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), DISPATCH_FLAG(YI, il, hipLaunchKernelGGL((gmgk::gs_color_residual<D, C16, (YI && D > 1)>), dim3(grid_for(se - sb)),
+                                     dim3(gmgk::kBlock), 0, h->stream, l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, out, l.n_pad, sb, se,
                                      h->cfg.gs_omega, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg()))));
-    h->fuse_res_from = sb;
-    return true;
+    return sb;
 }
 
 inline bool polled(gmg_handle h);
@@ -128,38 +147,39 @@ inline int first_color(const Level& l) {
 
 // Head of the next cycle: may the first colour launch of the level-0 pre-smoothing be enqueued ahead of the solve loop's decision?  Stream
 // launches with the polled check (the reduction publishes the decision), fp64, colour-major level 0 with a colour class in front of the one the
-// residual rides on, one group of columns, the whole system on this device.
+// residual rides on, one group of columns, the whole system on this device.  The loop that enqueues a head (enqueue_head) tells the next
+// cycle so (vcycle_resident's head_done -> SmoothAsk::head_done): its level-0 pre-smoothing then starts with its second launch.
 inline bool head_eligible(gmg_handle h, int d) {
     return h->cfg.speculate_head && polled(h) && !h->cfg.inner_precision && h->cfg.smoother == GMG_SMOOTHER_MULTICOLOR_GS && h->cfg.pre_iters > 0 && h->L >= 1 &&
            !h->lv[0].ord.blocked && h->lv[0].ord.n_colors >= 2 && first_color(h->lv[0]) >= 0 && first_color(h->lv[0]) < h->lv[0].ord.n_colors - 1 && d >= 1 && d <= 4 &&
            !h->partitioned && h->part_world <= 1 && h->d_watch && !h->prof_on;
 }
-inline void enqueue_head(gmg_handle h, int d) {
+// (returns true: the head is in the stream, what the caller hands to the next cycle)
+inline bool enqueue_head(gmg_handle h, int d) {
     Level& l = h->lv[0];
     const int c = first_color(l);
     launch_gs_color<double>(h, l, 0, d, l.ord.color_begin[c] / 64, l.ord.color_begin[c + 1] / 64, level_omega<double>(h, l), nullptr, reinterpret_cast<const int*>(h->d_watch + 1));
-    h->head_enqueued = true;
     h->timing["heads_enqueued"] += 1.0;
+    return true;
 }
 
 template <class T>
-void launch_gs_sweeps(gmg_handle h, Level& l, int d, int iters) {
-    const bool fine = &l == &h->lv[0];
-    // (the first launch of this cycle is already in the stream: enqueue_head)
-    const bool skip_head = fine && h->head_enqueued;
-    if (fine) h->head_enqueued = false;
-    const int c_head = skip_head ? first_color(l) : -1;
+SmoothDone<T> launch_gs_sweeps(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask) {
+    SmoothDone<T> done;
+    const int c_head = ask.head_done ? first_color(l) : -1;      // (the first launch of this cycle is already in the stream: enqueue_head)
     for (int it = 0; it < iters; ++it)
         for_col_chunks(d, [&](int c0, int dc) {
             for (int c = 0; c < l.ord.n_colors; ++c) {
                 int sb = l.ord.color_begin[c] / 64, se = l.ord.color_begin[c + 1] / 64;
                 if (se <= sb) continue;
                 if (it == 0 && c0 == 0 && c == c_head) continue;
-                if (fold_norm<T>(h, l, d, it == iters - 1 && c == l.ord.n_colors - 1, sb, se)) continue;
-                if (fold_residual<T>(h, l, d, it == iters - 1 && c == l.ord.n_colors - 1, sb, se)) continue;
+                const bool last_launch = it == iters - 1 && c == l.ord.n_colors - 1;
+                if (const int nblk = fold_norm<T>(h, l, d, last_launch, sb, se, ask.norm_type)) { done.norm_blocks = nblk; continue; }
+                if (const int from = fold_residual<T>(h, l, d, last_launch, sb, se, ask.res_out, ask.res_il)) { done.res_from = from; continue; }
                 launch_gs_color<T>(h, l, c0, dc, sb, se, level_omega<T>(h, l));
             }
         });
+    return done;
 }
 
 template <class T>
@@ -253,50 +273,48 @@ void launch_block_sweep_range(gmg_handle h, Level& l, int d, const T* in, T* out
 }
 
 template <class T>
-void launch_block_sweeps(gmg_handle h, Level& l, int d, int iters, bool from_zero = false) {
+SmoothDone<T> launch_block_sweeps(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask) {
+    SmoothDone<T> done;
     const int ld = l.n_pad;
     const int nb = l.ord.n_blocks();
     // from_zero: the iterate is the zero vector (the coarse correction's initial guess, multigrid_solver.cpp:1072-1073): the
     // first sweep gets no input vector -- it neither reads x nor gathers the off-block couplings (all zero) -- and the
     // caller skips the memset
-    T* in = from_zero ? nullptr : Prec<T>::x(l); T* out = Prec<T>::tmp(l);
+    T* in = ask.from_zero ? nullptr : Prec<T>::x(l); T* out = Prec<T>::tmp(l);
     const T* before_last = nullptr;      // the iterate the last sweep started from (nullptr: the zero vector)
     bool last_known = false;
-    T* il = (T*)h->il_sweep_out;          // (enqueue_up: the last sweep also writes the level's x as an interleaved multi-vector)
-    h->il_sweep_out = nullptr; h->il_sweep_done = false;
     int it0 = 0;
-    const bool first_fused = from_zero && h->first_sweep_fused;
-    h->first_sweep_fused = false;                  // (consumed by the level it was set for -- or void)
-    if (first_fused) {                             // the restriction into this level already ran the first sweep (launch_restrict_sweep0): its result is in tmp
+    if (ask.from_zero && ask.first_done) {         // the restriction into this level already ran the first sweep (launch_restrict_sweep0): its result is in tmp
         before_last = nullptr; last_known = true;
         in = out; out = Prec<T>::x(l);
         it0 = 1;
     }
     for (int it = it0; it < iters; ++it) {
-        const bool with_il = il && it == iters - 1 && l.use_ep && d > 1 && d <= 4;
-        launch_block_sweep_range<T>(h, l, d, in, out, 0, nb, nullptr, nullptr, with_il ? il : nullptr);
-        if (with_il) h->il_sweep_done = true;
+        // (il_out: the last sweep also writes the level's x as an interleaved multi-vector)
+        const bool with_il = ask.il_out && it == iters - 1 && l.use_ep && d > 1 && d <= 4;
+        launch_block_sweep_range<T>(h, l, d, in, out, 0, nb, nullptr, nullptr, with_il ? ask.il_out : nullptr);
+        if (with_il) done.il_written = true;
         before_last = in; last_known = true;
-        if (it == 0 && from_zero) { in = out; out = Prec<T>::x(l); }      // the result of sweep 1 is in tmp; ping-pong from there
+        if (it == 0 && ask.from_zero) { in = out; out = Prec<T>::x(l); }      // the result of sweep 1 is in tmp; ping-pong from there
         else std::swap(in, out);
     }
     if (in != Prec<T>::x(l)) (void)hipMemcpyAsync(Prec<T>::x(l), in, sizeof(T) * (size_t)ld * d, hipMemcpyDeviceToDevice, h->stream);
     // what residual_delta_ep needs: the last sweep went before_last -> x (the copy above, if any, does not touch before_last)
-    h->sweep_prev_valid = last_known && before_last != (const T*)Prec<T>::x(l);
-    h->sweep_prev = (const void*)before_last;
+    done.prev_valid = last_known && before_last != (const T*)Prec<T>::x(l);
+    done.prev = before_last;
+    return done;
 }
 
-// r = b - A x of a blocked level with the unpadded block storage, straight after its block sweeps (h->sweep_prev: the iterate the
+// r = b - A x of a blocked level with the unpadded block storage, straight after its block sweeps (swept: their result -- the iterate the
 // last sweep started from): the sweep's explicit part applied to x_old - x_new (kernels.hip.hpp::residual_delta_ep)
 // (begin_table / nb_list: an explicit list of blocks -- a rank's blocks of a partitioned level -- instead of all of them)
 template <class T>
-bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const int* begin_table = nullptr, int nb_list = 0) {
-    if (!l.use_ep || !h->sweep_prev_valid || pointwise_smoother(h->cfg)) return false;
-    h->sweep_prev_valid = false;
+bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const SmoothDone<T>& swept, const int* begin_table = nullptr, int nb_list = 0) {
+    if (!l.use_ep || !swept.prev_valid || pointwise_smoother(h->cfg)) return false;
     const int ld = l.n_pad, nb = begin_table ? nb_list : l.ord.n_blocks();
     if (nb <= 0) return true;
     const int grid = (nb + 7) / 8 * 8;
-    const T* x_old = (const T*)h->sweep_prev;
+    const T* x_old = swept.prev;
     const T* x_new = Prec<T>::x(l);
     for_col_chunks(d, [&](int c0, int dc) {
         DISPATCH_D(dc, DISPATCH_FLAG(STREAM, ep_streams(l), hipLaunchKernelGGL((gmgk::residual_delta_ep<T, D, STREAM>), dim3(grid), dim3(64),
@@ -312,12 +330,13 @@ inline bool smooth_from_zero_ok(gmg_handle h, const Level& l, int iters) {
 }
 
 template <class T = double>
-void launch_smooth(gmg_handle h, Level& l, int d, int iters, bool from_zero = false) {
-    if (iters <= 0) return;
+SmoothDone<T> launch_smooth(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask = {}) {
+    if (iters <= 0) return {};
     if (h->cfg.smoother == GMG_SMOOTHER_JACOBI) launch_jacobi_sweeps<T>(h, l, d, iters);
     else if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV) launch_cheby_steps<T>(h, l, d, iters);
-    else if (l.ord.blocked) launch_block_sweeps<T>(h, l, d, iters, from_zero);
-    else launch_gs_sweeps<T>(h, l, d, iters);
+    else if (l.ord.blocked) return launch_block_sweeps<T>(h, l, d, iters, ask);
+    else return launch_gs_sweeps<T>(h, l, d, iters, ask);
+    return {};
 }
 
 // y = A x (mode 0) or y = b - A x (mode 1) on the slices [sb, se) of level l
@@ -381,7 +400,7 @@ void launch_restrict(gmg_handle h, Level& fine, Level& coarse, int d, const T* s
 // coarse.b = U^T fine.r AND the first pre-sweep of the coarse level from the zero iterate, in one launch (kernels.hip.hpp::restrict_sweep0), where the
 // layouts allow it: the coarse level runs the entry-parallel block sweep on blocks b = rows 64 b .., its restriction has the quad layout with
 // 64-row sorting windows (a workgroup's four slices = one block), and the level's pre-smoothing starts from zero.  The coarse level's
-// launch_block_sweeps then starts with its second sweep (h->first_sweep_fused).
+// launch_block_sweeps then starts with its second sweep (SmoothAsk::first_done, from restrict_into's return value).
 // which fused form the restriction into `coarse` takes: 0 none, 1 restrict_sweep0 (entry-parallel sweep), 2 gs_block4<.., FR = true> (quad layout)
 template <class T>
 int restrict_sweep0_kind(gmg_handle h, const Level& fine, const Level& coarse, int d, bool src_il) {
@@ -474,14 +493,18 @@ int wait_norm(gmg_handle h) {
     return GMG_OK;
 }
 
+// What the check's reduction needs to take the loop's decision on the device (gmgk::SolveWatch): mode 0 a fixed number of cycles, 1 the rule of
+// solve_rule.hpp; cycles done including this one.  The loops that enqueue heads hand one to vcycle_resident with every cycle; nobody else does.
+struct CycleWatch { int mode; double tol; int type; int cycles_done; };
+
 // the reduction of one group of <= 4 columns: into h_norm + flag when polled, into d_norm (+ a copy later) otherwise
-// (partials: whose block sums -- the norm kernels' by default)
-void launch_reduce(gmg_handle h, int nblk, int dc, int c0, bool last, const double* partials = nullptr) {
+// (partials: whose block sums -- the norm kernels' by default; decide: also take the loop's decision, see CycleWatch)
+void launch_reduce(gmg_handle h, int nblk, int dc, int c0, bool last, const double* partials = nullptr, const CycleWatch* decide = nullptr) {
     if (!partials) partials = h->d_partials;
     if (polled(h)) {
         gmgk::SolveWatch watch{nullptr, nullptr, nullptr, 0.0, 0, 0, 0, 0};
-        if (h->watch_active && last && c0 == 0 && h->d_watch)         // (one group of columns: the kernel sees every sum the decision needs)
-            watch = gmgk::SolveWatch{reinterpret_cast<int*>(h->d_watch + 1), h->h_flag + 1, h->d_watch, h->watch_tol, h->watch_mode, h->watch_type, dc, h->watch_cycles_done};
+        if (decide && last && c0 == 0 && h->d_watch)         // (one group of columns: the kernel sees every sum the decision needs)
+            watch = gmgk::SolveWatch{reinterpret_cast<int*>(h->d_watch + 1), h->h_flag + 1, h->d_watch, decide->tol, decide->mode, decide->type, dc, decide->cycles_done};
         hipLaunchKernelGGL(gmgk::reduce_partials, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, partials, nblk, 2 * dc, h->h_norm + 2 * c0,
                            last ? h->h_flag : nullptr, last ? ++h->flag_seq[0] : 0ull, (int)EnvSwitches::get().publish_fenced, watch);
     }
@@ -490,13 +513,11 @@ void launch_reduce(gmg_handle h, int nblk, int dc, int c0, bool last, const doub
                            (unsigned long long*)nullptr, 0ull, 0);
 }
 
-// sums of w r^2 / w b^2 per column -> h_norm[2*d] (after wait_norm)
-int launch_norm(gmg_handle h, int d, int type) {
+// sums of w r^2 / w b^2 per column -> h_norm[2*d] (after wait_norm).  folded: partial-sum blocks the cycle's last colour launch already produced
+// for the rows of the last colour (fold_norm; 0: none); decide: launch_reduce
+int launch_norm(gmg_handle h, int d, int type, int folded = 0, const CycleWatch* decide = nullptr) {
     Level& l = h->lv[0];
     const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
-    // (rows of the last colour: already summed by the cycle's last colour launch when it was folded in, fold_norm)
-    const int folded = h->fuse_norm_blocks;
-    h->fuse_norm_blocks = 0;
     const int n_slices = folded ? l.ord.color_begin[l.ord.n_colors - 1] / 64 : l.Aoff.n_slices;
     const int nblk = norm_grid(n_slices);                // one slice per wave, like the residual SpMV; one partial per block of 16
     const bool poll = polled(h);
@@ -504,7 +525,7 @@ int launch_norm(gmg_handle h, int d, int type) {
         DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices<D, 0, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
                                           l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * l.n_pad, l.x + (size_t)c0 * l.n_pad, w,
                                           l.n_pad, n_slices, (float*)nullptr, h->d_partials, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
-        launch_reduce(h, nblk + folded, dc, c0, c0 + 4 >= d);
+        launch_reduce(h, nblk + folded, dc, c0, c0 + 4 >= d, nullptr, decide);
     });
     if (!poll) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
@@ -725,67 +746,66 @@ inline void prof_mark(gmg_handle h) {
 }
 
 // coarse.b = U_k^T r_k (:1069) into level k + 1 -- together with that level's first pre-sweep where the layouts allow the two in one launch
-// (restrict_sweep0_kind; the level's launch_block_sweeps then starts with its second sweep: h->first_sweep_fused)
+// (restrict_sweep0_kind).  Returns whether it did: the level's launch_block_sweeps then starts with its second sweep (SmoothAsk::first_done)
 template <class T>
-void restrict_into(gmg_handle h, int k, int d, bool il) {
+bool restrict_into(gmg_handle h, int k, int d, bool il) {
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
     const int fused = (k + 1 < h->L && smooth_from_zero_ok(h, c, h->cfg.pre_iters)) ? restrict_sweep0_kind<T>(h, l, c, d, il) : 0;
-    if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); h->first_sweep_fused = true; }
+    if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); }
     else launch_restrict<T>(h, l, c, d, Prec<T>::r(l), Prec<T>::b(c), il);
+    return fused != 0;
 }
 
+// the way down from level k0.  first_done: the caller's restriction into level k0 ran that level's first pre-sweep (restrict_into's return
+// value: a caller that starts below level 0 restricted into level k0 itself); head_done: level 0's first colour launch is in the stream
 template <class T = double>
-void enqueue_down(gmg_handle h, int d, int k0 = 0) {
+void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, bool head_done = false) {
     const int L = h->L;
-    if (k0 == 0) h->first_sweep_fused = false;     // (set by restrict_into for the level that follows; a caller that starts lower restricted into level k0 itself)
     for (int k = k0; k < L; ++k) {
         Level& l = h->lv[k];
         prof_mark(h);
-        const bool from_zero = k > 0 && smooth_from_zero_ok(h, l, h->cfg.pre_iters);      // eps.setZero (:1072-1073) folded into the first sweep
-        if (k > 0 && !from_zero) (void)hipMemsetAsync(Prec<T>::x(l), 0, sizeof(T) * (size_t)l.n_pad * d, h->stream);
-        // level 0, fp64: the last colour launch of the pre-smoothing also writes the residual of its rows (fold_residual)
-        constexpr bool no_fold = false;
+        SmoothAsk<T> ask;
+        ask.from_zero = k > 0 && smooth_from_zero_ok(h, l, h->cfg.pre_iters);      // eps.setZero (:1072-1073) folded into the first sweep
+        if (k > 0 && !ask.from_zero) (void)hipMemsetAsync(Prec<T>::x(l), 0, sizeof(T) * (size_t)l.n_pad * d, h->stream);
+        ask.first_done = first_done; ask.head_done = k == 0 && head_done;
         // d = 2 .. 4: the level-0 residual is written as an INTERLEAVED multi-vector (n x d row-major) -- only the restriction reads it, and a
         // gathered child then costs one cache line instead of d
-        constexpr bool no_il = false;
-        const bool il = k == 0 && d > 1 && d <= 4 && !no_il && l.Aoff.lpr == 1;
-        h->il_r0 = il;
-        if (k == 0 && sizeof(T) == 8 && !no_fold) h->fuse_res_out = h->lv[0].r;
-        h->fuse_res_from = 0;
-        h->sweep_prev_valid = false;
-        launch_smooth<T>(h, l, d, h->cfg.pre_iters, from_zero);                                     // :1063
-        h->fuse_res_out = nullptr;
-        const int res_slices = (k == 0 && h->fuse_res_from > 0) ? h->fuse_res_from : -1;
-        h->fuse_res_from = 0;
+        const bool il = k == 0 && d > 1 && d <= 4 && l.Aoff.lpr == 1;
+        // level 0, fp64: the last colour launch of the pre-smoothing also writes the residual of its rows (fold_residual)
+        if (k == 0 && sizeof(T) == 8) { ask.res_out = Prec<T>::r(l); ask.res_il = il; }
+        const SmoothDone<T> swept = launch_smooth<T>(h, l, d, h->cfg.pre_iters, ask);                // :1063
+        const int res_slices = (k == 0 && swept.res_from > 0) ? swept.res_from : -1;
         // :1066.  Straight after block sweeps on the unpadded block storage the residual comes from the sweep's explicit part alone
-        if (!(k > 0 && launch_residual_delta<T>(h, l, d, Prec<T>::r(l))))
+        if (!(k > 0 && launch_residual_delta<T>(h, l, d, Prec<T>::r(l), swept)))
             launch_spmv<T>(h, l, d, 1, Prec<T>::b(l), Prec<T>::x(l), Prec<T>::r(l), res_slices, il);
         // :1069 (+ the first pre-sweep of level k + 1 where the layouts allow the two in one launch)
-        restrict_into<T>(h, k, d, il);
-        h->il_r0 = false;
+        first_done = restrict_into<T>(h, k, d, il);
     }
     prof_mark(h);
 }
 
+// the way up to level k0.  norm_type >= 0: the check the cycle ends with, which level 0's last colour launch may join; returns fold_norm's blocks
 template <class T = double>
-void enqueue_up(gmg_handle h, int d, int k0 = 0) {
+int enqueue_up(gmg_handle h, int d, int k0 = 0, int norm_type = -1) {
     prof_mark(h);
+    int norm_blocks = 0;
+    bool il = false;
     for (int k = h->L - 1; k >= k0; --k) {
         Level& l = h->lv[k];
         // d = 2 .. 4: level 1's last post-sweep left a second, interleaved copy of its x in its (idle) residual vector: the prolongation into
         // level 0 gathers a parent's d values from one cache line
-        const bool il = k == 0 && h->il_sweep_done;
-        h->il_sweep_done = false;
         const T* src = il ? Prec<T>::r(h->lv[k + 1]) : Prec<T>::x(h->lv[k + 1]);
         launch_prolong_add<T>(h, l, h->lv[k + 1], d, src, Prec<T>::x(l), il);     // :1082
-        constexpr bool no_il = false;
-        if (k == 1 && k0 == 0 && d > 1 && d <= 4 && !no_il && h->cfg.post_iters > 0 && l.ord.blocked && l.use_ep && !pointwise_smoother(h->cfg))
-            h->il_sweep_out = (void*)Prec<T>::r(l);
-        launch_smooth<T>(h, l, d, h->cfg.post_iters);                                                // :1085
-        h->il_sweep_out = nullptr;
+        SmoothAsk<T> ask;
+        if (k == 1 && k0 == 0 && d > 1 && d <= 4 && h->cfg.post_iters > 0 && l.ord.blocked && l.use_ep && !pointwise_smoother(h->cfg))
+            ask.il_out = Prec<T>::r(l);
+        if (k == 0) ask.norm_type = norm_type;
+        const SmoothDone<T> swept = launch_smooth<T>(h, l, d, h->cfg.post_iters, ask);               // :1085
+        il = swept.il_written; norm_blocks = swept.norm_blocks;
         prof_mark(h);
     }
+    return norm_blocks;
 }
 
 // (n = 0 -- the block-CSR of a level that is one block has no entry -- is no launch: a grid of 0 workgroups is refused, and the error it leaves
@@ -1005,54 +1025,49 @@ int run_graph(gmg_handle h, int key, F&& enqueue) {
 
 // One V-cycle on the resident problem; norm_type >= 0 also enqueues the residual check of that type
 // (result in h_norm after the stream is synchronised by the caller).
+// What the loop around the cycle knows -- head_done: this cycle's first colour launch is already in the stream (enqueue_head: never under a
+// graph); decide: the check's reduction also takes the loop's decision (CycleWatch; not the mixed-precision check: no head is eligible there).
 template <class T>
-int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt) {
+int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, bool head_done, const CycleWatch* decide) {
     int rc;
     const int nt = norm_type < 0 ? 9 : norm_type;
     constexpr bool mixed = sizeof(T) == 4;
-    // the residual check's sums over the rows of the last colour come out of the last colour launch of the post-smoothing
-    constexpr bool no_fold = false;
-    const bool foldable = !mixed && !no_fold && norm_type >= 0 && h->cfg.post_iters > 0 && h->cfg.smoother == GMG_SMOOTHER_MULTICOLOR_GS && !h->lv[0].ord.blocked;
+    // the residual check's sums over the rows of the last colour come out of the last colour launch of the post-smoothing (fold_type >= 0)
+    const bool foldable = !mixed && norm_type >= 0 && h->cfg.post_iters > 0 && h->cfg.smoother == GMG_SMOOTHER_MULTICOLOR_GS && !h->lv[0].ord.blocked;
+    const int fold_type = foldable ? norm_type : -1;
     // mixed precision: the fp32 cycle starts from a zero guess on the defect b32 = b - A x (already in place), its
     // result is added to the fp64 iterate, and the new defect + its norms are formed in one fp64 pass
     auto head = [&] { if (mixed) (void)hipMemsetAsync(h->lv[0].x32, 0, sizeof(float) * (size_t)h->lv[0].n_pad * d, h->stream); };
-    auto tail = [&](int& err) {
+    // (folded: what the way up returned -- both in one enqueue body, which under a graph runs at capture only)
+    auto tail = [&](int& err, int folded) {
         if (mixed) {
             const size_t cnt = (size_t)h->lv[0].n_pad * d;
             hipLaunchKernelGGL(gmgk::add_correction, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->lv[0].x32, h->lv[0].x, (int64_t)cnt);
             err = launch_residual_to_f32(h, d, norm_type);
-        } else if (norm_type >= 0) err = launch_norm(h, d, norm_type);
+        } else if (norm_type >= 0) err = launch_norm(h, d, norm_type, folded, decide);
         prof_mark(h);
     };
     if (h->coarse_device) {
         int err = GMG_OK;
         rc = run_graph(h, key_salt + G_FULL * 10000 + d * 10 + nt, [&] {
             head();
-            enqueue_down<T>(h, d);
+            enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done);
             enqueue_coarse_device<T>(h, d);
-            h->fuse_norm_type = foldable ? norm_type : -1;
-            enqueue_up<T>(h, d);
-            h->fuse_norm_type = -1;
-            tail(err);
+            tail(err, enqueue_up<T>(h, d, 0, fold_type));
         });
         return rc ? rc : err;
     }
-    if ((rc = run_graph(h, key_salt + G_DOWN * 10000 + d * 10, [&] { head(); enqueue_down<T>(h, d); }))) return rc;
+    if ((rc = run_graph(h, key_salt + G_DOWN * 10000 + d * 10, [&] { head(); enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done); }))) return rc;
     if ((rc = coarse_host_begin<T>(h, d))) return rc;              // (polled: the way up is enqueued behind a gate the host opens in _serve)
     int err = GMG_OK;
-    rc = run_graph(h, key_salt + G_UP * 10000 + d * 10 + nt, [&] {
-        h->fuse_norm_type = foldable ? norm_type : -1;
-        enqueue_up<T>(h, d);
-        h->fuse_norm_type = -1;
-        tail(err);
-    });
+    rc = run_graph(h, key_salt + G_UP * 10000 + d * 10 + nt, [&] { tail(err, enqueue_up<T>(h, d, 0, fold_type)); });
     const int served = coarse_host_serve(h);
     return rc ? rc : (served ? served : err);
 }
 
-int vcycle_resident(gmg_handle h, int d, int norm_type) {
-    if (h->cfg.inner_precision) return vcycle_legs<float>(h, d, norm_type, 100000);
-    return vcycle_legs<double>(h, d, norm_type, 0);
+int vcycle_resident(gmg_handle h, int d, int norm_type, bool head_done = false, const CycleWatch* decide = nullptr) {
+    if (h->cfg.inner_precision) return vcycle_legs<float>(h, d, norm_type, 100000, head_done, decide);
+    return vcycle_legs<double>(h, d, norm_type, 0, head_done, decide);
 }
 
 // ---- accelerated solve loop (gmg_config::accelerate; engine.hip::solve_common; kernels: accel_kernels.hip.hpp) ----------------------

@@ -790,7 +790,8 @@ int p2p_smooth(gmg_handle h, int iters) {
 // `iters` block sweeps on this rank's blocks of level 1, each followed by the x1 halo exchange; the result ends in l1.x
 // (from_zero: the iterate is the zero vector and the first sweep takes no input, like launch_block_sweeps).
 // first_fused: the first (from-zero) sweep already ran inside the restriction's launch (restrict_sweep0 on this rank's blocks): its result is in tmp
-int p2p_smooth_level1(gmg_handle h, int iters, bool from_zero, bool first_fused = false) {
+// swept (optional): receives the iterate the last sweep started from, for the launch_residual_delta that follows
+int p2p_smooth_level1(gmg_handle h, int iters, bool from_zero, bool first_fused = false, SmoothDone<double>* swept = nullptr) {
     DistP2P* p = h->p2p;
     Level& l1 = h->lv[1];
     const int C = dist_classes(h->lv[0].ord), d = p->d, nb = (int)p->own_blocks[p->rank].size();
@@ -808,8 +809,7 @@ int p2p_smooth_level1(gmg_handle h, int iters, bool from_zero, bool first_fused 
     if (iters > 0 && in != l1.x) HIPCHK(hipMemcpyAsync(l1.x, in, sizeof(double) * (size_t)l1.n_pad * d, hipMemcpyDeviceToDevice, h->stream));
     // (both buffers carry the halo entries this rank's rows read: each was exchanged right after the sweep that wrote it -- what the
     // residual from the sweep's explicit part needs, launch_residual_delta, exactly as the single-GPU engine forms it)
-    h->sweep_prev_valid = iters > 0 && before_last != l1.x;
-    h->sweep_prev = (const void*)before_last;
+    if (swept) { swept->prev_valid = iters > 0 && before_last != l1.x; swept->prev = before_last; }
     return GMG_OK;
 }
 
@@ -829,13 +829,13 @@ int p2p_coarse_cycle_sharded(gmg_handle h) {
     if (fuse) launch_restrict_sweep0<double>(h, l0, l1, d, l0.r, false, 1, p->d_own_blocks, (int)p->own_blocks[p->rank].size());
     else if (p->n_rsl > 0) launch_restrict_list<double>(h, l0, l1, d, l0.r, l1.b, p->d_rsl, p->n_rsl);
     if (!from_zero) HIPCHK(hipMemsetAsync(l1.x, 0, sizeof(double) * (size_t)l1.n_pad * d, h->stream));       // :1072-1073
-    if ((rc = p2p_smooth_level1(h, h->cfg.pre_iters, from_zero, fuse))) return rc;        // :1063
-    const bool from_sweep = launch_residual_delta<double>(h, l1, d, l1.r, p->d_own_begin, (int)p->own_blocks[p->rank].size());      // :1066 on my rows ...
+    SmoothDone<double> swept;
+    if ((rc = p2p_smooth_level1(h, h->cfg.pre_iters, from_zero, fuse, &swept))) return rc;        // :1063
+    const bool from_sweep = launch_residual_delta<double>(h, l1, d, l1.r, swept, p->d_own_begin, (int)p->own_blocks[p->rank].size());      // :1066 on my rows ...
     if (!from_sweep && p->n_asl > 0) launch_spmv_list<double>(h, l1, d, l1.b, l1.x, l1.r, p->d_asl, p->n_asl);      // ... or with the residual SpMV
     if ((rc = p2p_exchange(h, C + 4, l1.r, l1.n_pad))) return rc;                      // everybody's rows -> complete r1 on every rank
-    h->first_sweep_fused = false;
-    restrict_into<double>(h, 1, d, false);                                            // :1069, replicated from here down (+ level 2's first sweep where fused)
-    enqueue_down<double>(h, d, 2);
+    const bool first_done = restrict_into<double>(h, 1, d, false);                    // :1069, replicated from here down (+ level 2's first sweep where fused)
+    enqueue_down<double>(h, d, 2, first_done);
     if (h->coarse_device) enqueue_coarse_device<double>(h, d);
     else if ((rc = coarse_host_begin<double>(h, d))) return rc;       // the host half is served at the end of the cycle's enqueue (p2p_vcycle)
     enqueue_up<double>(h, d, 2);

@@ -250,26 +250,17 @@ struct gmg_solver_s {
     } accel;
     // Head of the next cycle (gmg_config::speculate_head; engine.hip::solve_common): the solve loop's decision is taken by the check's
     // reduction on the device (d_watch: {double least; int go}), the first colour launch of the next cycle is enqueued behind it before the
-    // host has seen the norm, and returns at once when the iteration stopped.  watch_*: what the reduction needs to decide; head_enqueued:
-    // the next level-0 pre-smoothing starts with its second launch.
+    // host has seen the norm, and returns at once when the iteration stopped.  Only the device words live here: what the reduction needs to
+    // decide, and whether a head is in the stream, are the loop's locals and reach the launches as arguments (engine_cycle.hip.hpp: CycleWatch,
+    // vcycle_resident) -- like everything else one launch of a cycle hands to another (SmoothAsk / SmoothDone): the handle keeps no such state.
     double* d_watch = nullptr;
-    bool watch_active = false; int watch_mode = 0, watch_type = 0, watch_cycles_done = 0; double watch_tol = 0.0;
-    bool head_enqueued = false;
     double* h_pinned = nullptr; size_t pinned_cap = 0;     // coarse rhs / solution staging
     double* h_norm = nullptr;
     // polled completion (stream launches only): a kernel writes its small result into pinned memory and then a sequence
     // number into h_flag[slot]; the host spins on that word (wait_flag) instead of a copy + hipStreamSynchronize
-    // residual check folded into the last colour launch of the post-smoothing (engine_cycle.hip.hpp): type of the check the cycle
-    // being enqueued ends with (-1: none / not foldable), and the number of partial-sum blocks that launch produced (0: it did not)
-    int fuse_norm_type = -1, fuse_norm_blocks = 0;
-    // the same for the residual after the pre-smoothing: where the last colour launch shall write its rows' residual (null: nowhere),
-    // and the first slice it covered (0: it did not)
-    double* fuse_res_out = nullptr; int fuse_res_from = 0;
     unsigned long long* h_flag = nullptr; unsigned long long flag_seq[3] = {0, 0, 0};
     // h_flag[16]: written by the HOST -- the stream waits on it (hipStreamWaitValue64) in front of the work that needs the host's
     // coarsest solution, so that work is enqueued before the host solves (engine_cycle.hip.hpp::coarse_host_begin / _serve)
-    const void* sweep_prev = nullptr;    // the iterate the last block sweep of launch_block_sweeps started from (nullptr: zero) ...
-    bool sweep_prev_valid = false;       // ... valid until the next launch touches the level (enqueue_down consumes it: residual_delta_ep)
     bool gate_ok = true;                 // false once hipStreamWaitValue64 was refused: launch after the solve instead
     bool gate_proven = false;            // true once a published right-hand side was seen by the polling host while the stream was busy (ungated)
     bool coarse_pending = false;         // a gate is enqueued and the host has not answered it yet
@@ -281,7 +272,6 @@ struct gmg_solver_s {
     double* d_ainv = nullptr;                              // coarse_device: dense A_L^-1, level numbering (engine_system.hip.hpp::build_coarse_inverse_device)
     int ainv_n = 0, ainv_ld = 0;                           // ... n x n with rows ainv_ld doubles apart (n rounded up to 8: rows at 64-byte boundaries)
     int64_t fused_restrictions = 0;                       // restrictions enqueued together with the next level's first pre-sweep (restrict_into; timing key "restrict_sweeps_fused")
-    bool first_sweep_fused = false;                        // enqueue_down: the restriction into the next level ran that level's first pre-sweep (launch_restrict_sweep0)
     bool coarse_device = false;                            // the coarsest solve of the live system runs on the device (gmg_config::coarse_mode, decided per system)
     std::vector<double> coarse_work;
     std::unique_ptr<SpinTeam> coarse_helper;        // the other threads of the coarsest back-substitution, armed for the duration of a solve (HelperScope)
@@ -303,9 +293,6 @@ struct gmg_solver_s {
     int* d_rap_order2 = nullptr;
     std::vector<hipEvent_t> prof_ev;     // gmg_profile_cycle: events at the boundaries of a cycle's legs (prof_on: record them)
     bool prof_on = false; int prof_n = 0;
-    bool il_r0 = false;                   // enqueue_down, level 0, d > 1: the residual is being written as an interleaved multi-vector
-    void* il_sweep_out = nullptr;         // enqueue_up: where level 1's last post-sweep writes the interleaved copy of its x ...
-    bool il_sweep_done = false;           // ... and whether it did (the level-0 prolongation then gathers from it)
     // multi-GPU (one process per GPU): this rank's share of level 0, externally owned level-0 vectors
     hipStream_t own_stream = nullptr;
     int rank = 0, world = 1;
