@@ -152,6 +152,7 @@ SIGNATURES = {
 INTERNAL_SIGNATURES = {
     "gmg_debug_sell_info": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "gmg_debug_sell_copy": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _dp, _ip, _dp]),
+    "gmg_debug_col16_copy": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_uint), _ip]),
     "gmg_debug_select_parents": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip, _ip, C.c_int,
                                            C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), _ip, _dp]),
     "gmg_hierarchy_debug_row_kinds": (C.c_int, [_vp, C.c_int, _ip]),
@@ -505,6 +506,22 @@ class Engine:
         self._chk(lib().gmg_debug_sell_copy(self._h, int(k), int(which), sp_.ctypes.data_as(C.POINTER(C.c_int64)), _pi(col), _pd(val),
                                             _pi(row_of) if has_row_of else None, _pd(diag) if diag is not None else None))
         return {"n_slices": ns, "lpr": lpr, "slice_ptr": sp_, "col": col, "val": val, "row_of": row_of, "diag": diag}
+
+    def debug_col16(self, which: int) -> dict:
+        """The 16-bit column codes of a level-0 layout (0 A, 3 P, 4 R) copied back: windows per slice (0 / 8 / 32), mode, c16_from, uniform
+        width, the code words (indexed like debug_sell's col; of every slice's region only the first half was written) and win_base
+        (n_slices x windows); both arrays None where the layout has no codes."""
+        info = (C.c_int64 * 5)()
+        self._chk(lib().gmg_debug_col16_copy(self._h, int(which), info, None, None))
+        nw, mode, c16_from, uw, words = (int(v) for v in info)
+        out = {"windows": nw, "mode": mode, "from": c16_from, "uniform_width": uw, "col16": None, "win_base": None}
+        if nw:
+            sinfo = (C.c_int64 * 4)()
+            self._chk(lib().gmg_debug_sell_info(self._h, 0, int(which), sinfo))
+            col16 = np.zeros(words, np.uint32); wb = np.zeros((int(sinfo[0]), nw), np.int32)
+            self._chk(lib().gmg_debug_col16_copy(self._h, int(which), info, col16.ctypes.data_as(C.POINTER(C.c_uint)), _pi(wb)))
+            out["col16"], out["win_base"] = col16, wb
+        return out
 
     def debug_set(self, key: str, value: float):
         """Set-up fault injection for the tests (gravomg_hip_internal.h), effective from the next set_system."""

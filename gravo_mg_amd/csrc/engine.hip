@@ -412,6 +412,22 @@ int gmg_debug_sell_copy(gmg_handle h, int k, int which, int64_t* slice_ptr, int*
     return GMG_OK;
 } GMG_CATCH_H
 
+// The 16-bit column codes of a level-0 layout as gmgs::compress_cols left them (gravomg_hip_internal.h): plain copies of arrays the handle owns.
+int gmg_debug_col16_copy(gmg_handle h, int which, int64_t* info, unsigned* col16, int* win_base) try {
+    NEED_DEVICE();
+    int rc = check_level(h, 0, false);
+    if (rc) return rc;
+    if ((rc = check_whole_system(h))) return rc;
+    DevSell* s = (which == 0 || which == 3 || which == 4) ? pick_sell(h, 0, which) : nullptr;
+    if (!s || !info) return fail(h, GMG_ERR_INVALID, "bad arguments");
+    const int nw = s->col16 ? (s->c16_dbits == 13 ? 8 : 32) : 0;
+    info[0] = nw; info[1] = s->col16 ? s->c16_mode : 0; info[2] = s->c16_from; info[3] = s->uniform_w; info[4] = s->col16 ? s->stored : 0;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (col16 && s->col16) HIPCHK(hipMemcpy(col16, s->col16, sizeof(unsigned) * (size_t)s->stored, hipMemcpyDeviceToHost));
+    if (win_base && s->win_base) HIPCHK(hipMemcpy(win_base, s->win_base, sizeof(int) * (size_t)s->n_slices * nw, hipMemcpyDeviceToHost));
+    return GMG_OK;
+} GMG_CATCH_H
+
 int gmg_get_timing(gmg_handle h, const char* key, double* out) try {
     if (!h || !key || !out) return GMG_ERR_INVALID;
     if (std::string(key) == "device_bytes_now") { *out = (double)h->pool.live_bytes; return GMG_OK; }      // device memory the handle holds at this moment (pool blocks in use)

@@ -763,6 +763,10 @@ private:
     }
     // -- host-planned layouts: uploads in the order the stages complete (level 0 first: the largest, ready early)
     void host_uploads() {
+        // host-planned layouts carry no 16-bit column codes (upload_sell resets them): the keys must not keep what a device layout reported -- the
+        // one this call abandoned for rows too long for the device builder, or an earlier system's
+        for (const char* key : {"col16_l0", "col16_R_l0", "col16_P_l0"})
+            for (const char* sfx : {"", "_failed_slices", "_mode", "_windows", "_uniform_width"}) h->timing[std::string(key) + sfx] = 0.0;
         for (int k = 0; k <= L && rc_all == GMG_OK; ++k) {
             if (!ordering_arrived(k)) break;
             auto tu = clk::now();

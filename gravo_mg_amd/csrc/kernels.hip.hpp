@@ -41,6 +41,13 @@ __device__ __forceinline__ int wave_slice(int n_slices_total, int xcd_swizzle) {
 // row instead of D; round 4, level-0 restriction / prolongation at d > 1), XI = 0: column-major with leading dimension ld.
 template <int D, int XI> __device__ __forceinline__ int64_t x_at(int c, int d, int ld) { return XI ? (int64_t)c * D + d : c + (int64_t)d * ld; }
 
+// The accumulation of a row's dot product is written as fused multiply-adds, not left to the compiler's contraction: with "+= v * x" the fp32
+// instantiations for three right-hand sides came out as a mix of packed multiplies + adds and fused operations that was not the same mix in
+// every instantiation of the same source (the flagged code-reading variant against the one on 32-bit indices), so "the same columns in the same
+// order" did not give the same bits.  (The fp64 instantiations were fused throughout already: their code does not change.)
+__device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+__device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
+
 template <class T, int D, int W, int XI = 0>
 __device__ __forceinline__ void row_dot_group(const int* __restrict__ cp, const T* __restrict__ vp, const T* x, int ld,
                                               T (&acc)[D]) {
@@ -56,7 +63,7 @@ __device__ __forceinline__ void row_dot_group(const int* __restrict__ cp, const 
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
-        for (int d = 0; d < D; ++d) acc[d] += v[j] * xv[j][d];
+        for (int d = 0; d < D; ++d) acc[d] = fma_of(v[j], xv[j][d], acc[d]);
 }
 
 // acc[c] = sum_j val[j] * x[col[j] + c*ld] over this lane's row of slice s.  The slice width is wave-uniform, so
@@ -132,7 +139,7 @@ __device__ __forceinline__ void row_dot_group16(const unsigned* __restrict__ cp,
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
-        for (int d = 0; d < D; ++d) acc[d] += v[j] * xv[j][d];
+        for (int d = 0; d < D; ++d) acc[d] = fma_of(v[j], xv[j][d], acc[d]);
 }
 
 // row_dot with the columns read from the codes (G is even: a group's codes are whole words)

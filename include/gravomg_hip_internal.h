@@ -17,6 +17,12 @@ extern "C" {
  * NULL; col receives 32-bit columns also for the 16-bit A_in; diag (which = 0 only) the level's diagonal. */
 int gmg_debug_sell_info(gmg_handle h, int k, int which, int64_t* info);
 int gmg_debug_sell_copy(gmg_handle h, int k, int which, int64_t* slice_ptr, int* col, double* val, int* row_of, double* diag);
+/* The 16-bit column codes of a level-0 layout (which = 0, 3 or 4 as above; csrc/setup_kernels.hip.hpp::compress_cols) as the kernels read them.
+ * info[0..4] = windows per slice (0 no codes, 8 or 32), mode (0 none, 1 codes from slice info[2] on, 2 uncovered slices flagged), c16_from,
+ * uniform slice width (0: widths differ), stored words (= the layout's stored entries: of every slice's region the first half is used, the rest
+ * was never written).  Copy-out pointers may be NULL: call once for info, then with col16 of info[4] words and win_base of n_slices * info[0]
+ * entries.  Plain copies of arrays the handle owns; nothing is launched and the set-up is not touched. */
+int gmg_debug_col16_copy(gmg_handle h, int which, int64_t* info, unsigned* col16, int* win_base);
 
 /* Set-up fault injection for the tests, per handle, effective from the next gmg_set_system.  Keys:
  *   "col16_uncovered" = N > 0: every N-th level-0 slice is treated as not covered by its column windows (flagged one by one, c16 mode 2);

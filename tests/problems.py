@@ -57,16 +57,23 @@ def sphere_problem(n=6000, lower_bound=80, order="spatial"):
     return Problem(V, S, mass, H.U, lhs, rhs, f"sphere{n}-{order}")
 
 
-def _laplacian_of(W):
-    """Graph Laplacian S = diag(W 1) - W of a symmetric non-negative weight matrix (CSC, sorted)."""
-    W = sp.csc_matrix(W)
+def _laplacian_of(W, extra=None):
+    """Graph Laplacian S = diag(W 1) - W of a symmetric non-negative weight matrix (CSC, sorted); extra: a second weight matrix (further edges)
+    added to W first."""
+    W = sp.csc_matrix(W) if extra is None else sp.csc_matrix(W + extra)
     S = (sp.diags(np.asarray(W.sum(axis=1)).ravel()) - W).tocsc()
     S.sort_indices()
     return S
 
 
-def _weights(rows, cols, n, rng):
-    """Symmetric weight matrix with seeded weights in [0.5, 1.5) on the undirected edges (rows[i], cols[i])."""
+def _weights(rows, cols, n, rng, distinct=False):
+    """Symmetric weight matrix with seeded weights in [0.5, 1.5) on the undirected edges (rows[i], cols[i]).  distinct: loops are dropped and an
+    edge given twice (in either direction) is kept once -- for edge lists that were drawn at random."""
+    if distinct:
+        rows, cols = np.asarray(rows, np.int64), np.asarray(cols, np.int64)
+        keep = rows != cols
+        key = np.unique(np.minimum(rows, cols)[keep] * n + np.maximum(rows, cols)[keep])
+        rows, cols = key // n, key % n
     w = 0.5 + rng.random(len(rows))
     W = sp.coo_matrix((w, (rows, cols)), shape=(n, n)).tocsc()
     return W + W.T
@@ -101,7 +108,9 @@ def synthetic_problem(graph, sizes, kind="poisson", prolong=("pc",), d=8, seed=5
 
     graph: ("chain", n) | ("grid", n1, n2) | ("diagonal", n) | ("isolated", n1, n2) -- a grid with every 20th vertex cut loose (only its
     diagonal) | ("clique", n1, n2, m) -- a grid behind m vertices that form a clique, vertex i < m tied to grid vertex m + i | ("hub", n1, n2) --
-    a grid whose last vertex is tied to the first vertex of every level-1 group (a dense row on level 1).
+    a grid whose last vertex is tied to the first vertex of every level-1 group (a dense row on level 1) | ("links", n, ring, a, b) -- a chain
+    (ring: closed, n - 1 tied to 0) plus the long links a[i] <-> b[i] given as index arrays (loops and repeats are dropped); the chain keeps the
+    weights of ("chain", n).
     sizes: [n_0, n_1, ..., n_L]; prolong: "pc" (aggregation) or "smooth" (3-entry rows) per level, the last one repeated.
     kind: "poisson" lhs = S + 1e-2 M, "smoothing" lhs = M + S; M a positive lumped mass.  rhs = M y with d seeded columns."""
     rng = np.random.default_rng(seed)
@@ -127,10 +136,23 @@ def synthetic_problem(graph, sizes, kind="poisson", prolong=("pc",), d=8, seed=5
         g = _grid_edges(n1, n2, offset=m)
         a, b = np.triu_indices(m, 1)
         e = (np.concatenate([g[0], a, np.arange(m)]), np.concatenate([g[1], b, m + np.arange(m)]))
+    elif name == "links":
+        n, ring = graph[1], graph[2]
+        e = (np.arange(n - 1), np.arange(1, n))
+        la, lb = np.asarray(graph[3], np.int64), np.asarray(graph[4], np.int64)
+        assert la.shape == lb.shape and la.min(initial=0) >= 0 and lb.min(initial=0) >= 0 and la.max(initial=0) < n and lb.max(initial=0) < n
+        if ring:
+            la, lb = np.append(la, n - 1), np.append(lb, 0)
+        far = np.abs(la - lb) != 1                                 # (a link along the chain is the chain's edge)
+        extra = (la[far], lb[far])
     else:
         raise ValueError(graph)
     assert sizes[0] == n, (sizes, n)
-    S = _laplacian_of(_weights(e[0], e[1], n, rng)) if len(e[0]) else sp.csc_matrix((n, n))
+    if name == "links":
+        W = _weights(e[0], e[1], n, rng)
+        S = _laplacian_of(W, extra=_weights(extra[0], extra[1], n, rng, distinct=True))
+    else:
+        S = _laplacian_of(_weights(e[0], e[1], n, rng)) if len(e[0]) else sp.csc_matrix((n, n))
     mass = 0.5 + rng.random(n)
     if kind == "poisson":
         lhs = (S + 1e-2 * sp.diags(mass)).tocsc()
@@ -144,7 +166,8 @@ def synthetic_problem(graph, sizes, kind="poisson", prolong=("pc",), d=8, seed=5
     for k in range(len(sizes) - 1):
         how = prolong[min(k, len(prolong) - 1)]
         U.append(aggregation(sizes[k], sizes[k + 1]) if how == "pc" else smoothed_aggregation(sizes[k], sizes[k + 1]))
-    return Problem(None, S, mass, U, lhs, rhs, f"{'-'.join(map(str, graph))}-{kind}-{'x'.join(map(str, sizes))}")
+    label = graph if name != "links" else (name, graph[1], "ring" if graph[2] else "chain", len(graph[3]))
+    return Problem(None, S, mass, U, lhs, rhs, f"{'-'.join(map(str, label))}-{kind}-{'x'.join(map(str, sizes))}")
 
 
 def permuted_system(A, new2old):
