@@ -23,7 +23,7 @@ LIB_PATH = os.environ.get("GMG_LIB_PATH") or os.path.join(_HERE, "lib", "libgrav
 GMG_OK, GMG_ERR_INVALID, GMG_ERR_NO_DEVICE, GMG_ERR_HIP, GMG_ERR_STATE, GMG_ERR_NUMERIC, GMG_ERR_UNSUPPORTED = 0, -1, -2, -3, -4, -5, -6
 DIVERGED = 1          # gmg_solve only, not an error: the iteration did not contract
 SMOOTHER_MULTICOLOR_GS, SMOOTHER_JACOBI, SMOOTHER_CHEBYSHEV = 0, 1, 2
-COARSE_HOST_LDLT, COARSE_DEVICE_INVERSE, COARSE_AUTO = 0, 1, 2
+COARSE_HOST_LDLT, COARSE_DEVICE_INVERSE, COARSE_AUTO, COARSE_DEVICE_TRIANGLE = 0, 1, 2, 3
 
 _STATUS_NAMES = {
     -1: "GMG_ERR_INVALID", -2: "GMG_ERR_NO_DEVICE", -3: "GMG_ERR_HIP", -4: "GMG_ERR_STATE",

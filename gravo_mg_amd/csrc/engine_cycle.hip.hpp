@@ -845,6 +845,22 @@ void enqueue_coarse_device(gmg_handle h, int d) {
     Level& c = h->lv[h->L];
     const size_t cnt = (size_t)c.n_pad * d;
     if (sizeof(T) == 4) launch_cvt(h, c.b32, c.b, cnt);
+    if (h->coarse_triangle) {
+        // GMG_COARSE_DEVICE_TRIANGLE: two launches per column group (kernels.hip.hpp::tri_symv_items / tri_symv_reduce); the groups share the scratch,
+        // one after the other on the stream
+        const int nb = tri_blocks(c.n);
+        const bool nt = EnvSwitches::get().tri_nt;
+        if (nb > 0) for_col_chunks(d, [&](int c0, int dc) {
+            const double* b = c.b + (size_t)c0 * c.n_pad;
+            double* x = c.x + (size_t)c0 * c.n_pad;
+            DISPATCH_D(dc, DISPATCH_FLAG(NT, nt, hipLaunchKernelGGL((gmgk::tri_symv_items<D, NT>), dim3((unsigned)tri_item_count(nb)), dim3(gmgk::kBlock), 0, h->stream,
+                                          (const double*)h->d_tri, (const int*)h->d_tri_perm, c.n, b, c.n_pad, h->d_tri_row, h->d_tri_col)));
+            DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::tri_symv_reduce<D>), dim3(nb), dim3(gmgk::kBlock), 0, h->stream, (const double*)h->d_tri_row,
+                                          (const double*)h->d_tri_col, (const int*)h->d_tri_perm, c.n, nb, x, c.n_pad));
+        });
+        if (sizeof(T) == 4) launch_cvt(h, c.x, c.x32, cnt);
+        return;
+    }
     for_col_chunks(d, [&](int c0, int dc) {
         // rows per wave: the rows of a wave share the loads of the vectors (what bounds the product at d = 3 and at n_L beyond the L1's reach); a small
         // level keeps one row per wave -- it needs every wave it can get to cover the memory latency

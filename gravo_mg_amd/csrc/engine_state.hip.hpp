@@ -271,6 +271,12 @@ struct gmg_solver_s {
     bool poll = true;             // GMG_POLL=0: copy + hipStreamSynchronize instead (the waiting thread then sleeps instead of spinning)
     double* d_ainv = nullptr;                              // coarse_device: dense A_L^-1, level numbering (engine_system.hip.hpp::build_coarse_inverse_device)
     int ainv_n = 0, ainv_ld = 0;                           // ... n x n with rows ainv_ld doubles apart (n rounded up to 8: rows at 64-byte boundaries)
+    // GMG_COARSE_DEVICE_TRIANGLE instead: the packed lower triangle in the factor's numbering (coarse_triangle.hpp), the permutation factor -> level
+    // the product gathers and scatters through, and the product's row / column partials of one column group -- all made at set-up
+    double *d_tri = nullptr, *d_tri_row = nullptr, *d_tri_col = nullptr;
+    int* d_tri_perm = nullptr;
+    int tri_n = -1;                                        // n_L the four buffers are sized for (-1: none)
+    bool coarse_triangle = false;                          // coarse_device, applied from d_tri (decided per system)
     int64_t fused_restrictions = 0;                       // restrictions enqueued together with the next level's first pre-sweep (restrict_into; timing key "restrict_sweeps_fused")
     bool coarse_device = false;                            // the coarsest solve of the live system runs on the device (gmg_config::coarse_mode, decided per system)
     std::vector<double> coarse_work;
@@ -602,6 +608,12 @@ void unbind_level0(gmg_handle h) {
 
 void lose_live_system(gmg_handle h) { h->live = LiveSystem::none; }
 
+void free_coarse_triangle(gmg_handle h) {
+    for (double** p : {&h->d_tri, &h->d_tri_row, &h->d_tri_col}) if (*p) { (void)dev_free(*p); *p = nullptr; }
+    if (h->d_tri_perm) { (void)dev_free(h->d_tri_perm); h->d_tri_perm = nullptr; }
+    h->tri_n = -1;
+}
+
 void drop_system(gmg_handle h) {
     h->refill_ready = false;
     lose_live_system(h);
@@ -617,6 +629,7 @@ void drop_system(gmg_handle h) {
     if (h->d_minv) { (void)dev_free(h->d_minv); h->d_minv = nullptr; }
     if (h->d_ainv) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; }
     h->ainv_n = 0;
+    free_coarse_triangle(h);
 }
 
 // blocked levels smaller than this use 4 lanes per row (measured in round 4, profiles/r04/d_quad_threshold_ab.txt)

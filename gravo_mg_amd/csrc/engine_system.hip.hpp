@@ -117,17 +117,24 @@ int refresh_fp32_twins(gmg_handle h, bool alloc) {
 // lower_bound = 1000 / ratio = 8 keep n_L below 8 000).
 constexpr int kCoarseDeviceMax = 8192;
 bool want_coarse_device(gmg_handle h, int n_coarse) {
-    if (h->cfg.coarse_mode == GMG_COARSE_DEVICE_INVERSE) return true;
+    if (h->cfg.coarse_mode == GMG_COARSE_DEVICE_INVERSE || h->cfg.coarse_mode == GMG_COARSE_DEVICE_TRIANGLE) return true;
     return h->cfg.coarse_mode == GMG_COARSE_AUTO && n_coarse <= kCoarseDeviceMax;
 }
+// ... and from which matrix it is applied there: GMG_COARSE_DEVICE_TRIANGLE keeps the packed lower triangle only (coarse_triangle.hpp)
+bool want_coarse_triangle(gmg_handle h) { return h->cfg.coarse_mode == GMG_COARSE_DEVICE_TRIANGLE; }
 
 // Dense inverse of the coarsest operator, built ON THE DEVICE from the host's sparse factor (setup_kernels.hip.hpp::coarse_inverse_tiles): the factor
 // goes up in the device's chunk layout (a few MB), one launch carries every 64-column tile of the identity through it, a second one mirrors the
 // lower triangle, a third one moves it from the factor's numbering into the level's.  (Until round 6 the host solved n_L right-hand sides one by
 // one: 188 - 226 ms of set-up at n_L = 6 005.)
+// GMG_COARSE_DEVICE_TRIANGLE stops after the tiles: one launch packs the triangle they computed into 64 x 64 blocks, still in the factor's numbering
+// (setup_kernels.hip.hpp::pack_lower_blocks); the full matrix is not made, the permutation stays on the device for the product, and the product's
+// scratch is allocated here.
 int build_coarse_inverse_device(gmg_handle h) {
     auto t0 = clk::now();
     const int nl = h->coarse.n;
+    const bool tri_mode = want_coarse_triangle(h);
+    h->coarse_triangle = tri_mode;
     SupernodalLDLT::DeviceFactor E;
     h->coarse.export_device_factor(E);
     h->timing["coarse_inverse_export_ms"] = ms_since(t0);
@@ -153,14 +160,31 @@ int build_coarse_inverse_device(gmg_handle h) {
     std::vector<int> inv_h((size_t)nl);
     for (int i = 0; i < nl; ++i) inv_h[(size_t)E.perm[(size_t)i]] = i;
     DevTmp<int> perm_d, inv_d;
-    if ((rc = up(perm_d, E.perm)) || (rc = up(inv_d, inv_h))) return rc;
+    if (!tri_mode && ((rc = up(perm_d, E.perm)) || (rc = up(inv_d, inv_h)))) return rc;
     const size_t bytes = sizeof(double) * (size_t)nl * nl;
     DevTmp<double> X;                                       // the inverse in the factor's numbering
     if ((rc = X.alloc(h, std::max<size_t>((size_t)nl * nl, 1)))) return rc;
     const int lda = (nl + 7) / 8 * 8;
-    if (h->d_ainv && h->ainv_n != nl) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; }
-    if (!h->d_ainv) HIPCHK(dev_malloc((void**)&h->d_ainv, std::max<size_t>(sizeof(double) * (size_t)nl * lda, 8)));
-    h->ainv_n = nl; h->ainv_ld = lda;
+    const int nb = tri_blocks(nl);
+    if (tri_mode) {
+        if (h->d_ainv) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; h->ainv_n = 0; }
+        if (h->tri_n != nl) {
+            free_coarse_triangle(h);
+            HIPCHK(dev_malloc((void**)&h->d_tri, std::max<size_t>(sizeof(double) * (size_t)tri_block_count(nb) * kTriBlockDoubles, 8)));
+            HIPCHK(dev_malloc((void**)&h->d_tri_row, std::max<size_t>(sizeof(double) * (size_t)tri_row_scratch_doubles(nb), 8)));
+            HIPCHK(dev_malloc((void**)&h->d_tri_col, std::max<size_t>(sizeof(double) * (size_t)tri_col_scratch_doubles(nb), 8)));
+            HIPCHK(dev_malloc((void**)&h->d_tri_perm, std::max<size_t>(sizeof(int) * (size_t)nl, 8)));
+            h->tri_n = nl;
+        }
+        if (nl > 0 && (rc = h2d(h, h->d_tri_perm, E.perm.data(), sizeof(int) * (size_t)nl))) return rc;
+        h->timing["coarse_inverse_bytes"] = (double)(sizeof(double) * (size_t)tri_block_count(nb) * kTriBlockDoubles);
+    } else {
+        free_coarse_triangle(h);
+        if (h->d_ainv && h->ainv_n != nl) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; }
+        if (!h->d_ainv) HIPCHK(dev_malloc((void**)&h->d_ainv, std::max<size_t>(sizeof(double) * (size_t)nl * lda, 8)));
+        h->ainv_n = nl; h->ainv_ld = lda;
+        h->timing["coarse_inverse_bytes"] = (double)(sizeof(double) * (size_t)nl * lda);
+    }
     HIPCHK(hipMemsetAsync(X.p, 0, bytes, h->stream));
     gmgs::InvFactor F;
     F.n = nl; F.nq = E.nq; F.nlev = E.nlev;
@@ -176,10 +200,14 @@ int build_coarse_inverse_device(gmg_handle h) {
         else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.p);
         else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.p);
         (void)hipEventRecord(h->ev1, h->stream);
-        hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.p, nl);
-        // ... and into the level's numbering: the product kernel then reads its vectors contiguously
-        if (nl <= 8192) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X.p, (const int*)perm_d.p, (const int*)inv_d.p, nl, h->d_ainv, lda);
-        else hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X.p, (const int*)perm_d.p, nl, h->d_ainv, lda);
+        if (tri_mode) {
+            hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X.p, nl, h->d_tri);
+        } else {
+            hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.p, nl);
+            // ... and into the level's numbering: the product kernel then reads its vectors contiguously
+            if (nl <= 8192) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X.p, (const int*)perm_d.p, (const int*)inv_d.p, nl, h->d_ainv, lda);
+            else hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X.p, (const int*)perm_d.p, nl, h->d_ainv, lda);
+        }
     }
     HIPCHK(hipGetLastError());
     HIPCHK(hipStreamSynchronize(h->stream));        // (the temporaries above go back to the pool; the host copy E dies here)
@@ -249,6 +277,10 @@ int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, boo
     h->timing["coarsest_solve"] = ms_factor;
     h->coarse_device = want_coarse_device(h, h->lv[L].A.n_outer);
     h->timing["coarse_on_device"] = h->coarse_device ? 1.0 : 0.0;
+    h->coarse_triangle = h->coarse_device && want_coarse_triangle(h);
+    h->timing["coarse_triangle"] = h->coarse_triangle ? 1.0 : 0.0;
+    h->timing["coarse_triangle_run_blocks"] = h->coarse_triangle ? (double)kTriRun : 0.0;
+    if (!h->coarse_device) h->timing["coarse_inverse_bytes"] = 0.0;
     if (h->coarse_device && !inverse_ready && (rc = build_coarse_inverse_device(h))) return rc;
     if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV && !placeholder && (rc = compute_cheby_bounds(h))) return rc;      // (the real values bring the bounds: no keys before a gmg_set_system)
     if (h->cfg.inner_precision && (rc = refresh_fp32_twins(h, alloc_twins))) return rc;

@@ -94,6 +94,9 @@ struct Compressed {
 //   GMG_SYMV_ROWS=1|2|4     rows per wave of the coarsest level's dense product (default: by the level's size, engine_cycle.hip.hpp::symv_rows)
 //   GMG_SYMV_STRIDES=2|4|8  strides of 64 columns a lane of that product loads per trip (default 4)
 //   GMG_SYMV_V2=0           that product with 8-byte instead of 16-byte loads (measurement: scripts/symv_sweep.py)
+//   GMG_TRI_NT=1            GMG_COARSE_DEVICE_TRIANGLE's product with non-temporal instead of plain loads of the matrix (measurement:
+//                           scripts/coarse_triangle.py -- with plain loads the leg at n_L = 6 005, a 146 MB triangle, is 2.0 us shorter at d = 3 and
+//                           2.9 us at d = 1, profiles/coarse_triangle)
 //   GMG_CHEBY_RATIO=R       lambda_max / lambda_min of the Chebyshev smoother's interval (1 < R <= 1e6; default cheby_coeffs.hpp::kChebyRatio; any
 //                           other value is ignored with one line on stderr)
 // Everything else that used to be an A/B switch is either a gmg_config field or gone.
@@ -105,6 +108,7 @@ struct EnvSwitches {
     bool p2p_fence_free = false, publish_fenced = false, p2p_shared_device = false;
     int symv_rows = 0, symv_strides = 0;   // 0: the engine's choice
     bool symv_v2 = true;
+    bool tri_nt = false;                   // GMG_TRI_NT=1: non-temporal instead of plain loads of the packed triangle
     double cheby_ratio = 0.0;              // 0: cheby_coeffs.hpp::kChebyRatio
     static const EnvSwitches& get() {
         static const EnvSwitches v = [] {
@@ -124,6 +128,7 @@ struct EnvSwitches {
             e.symv_rows = std::max(0, (int)num("GMG_SYMV_ROWS"));
             e.symv_strides = std::max(0, (int)num("GMG_SYMV_STRIDES"));
             e.symv_v2 = (int)num("GMG_SYMV_V2") != 0;
+            e.tri_nt = (int)num("GMG_TRI_NT") > 0;
             if (const char* t = std::getenv("GMG_CHEBY_RATIO")) {
                 const double r = std::atof(t);
                 if (r > 1.0 && r <= 1e6) e.cheby_ratio = r;      // (cheby_coeffs.hpp::cheby_ratio_usable)

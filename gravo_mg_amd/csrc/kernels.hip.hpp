@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "solve_rule.hpp"
+#include "coarse_triangle.hpp"
 
 namespace gmgk {
 
@@ -1974,6 +1975,167 @@ __global__ __launch_bounds__(kBlock) void dense_symv_v2(const double* __restrict
             for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
             if (lane == 0 && row0 + r < n) y[row0 + r + (int64_t)c * ldv] = v;
         }
+}
+
+// GMG_COARSE_DEVICE_TRIANGLE: the same product from the packed lower triangle T of A_L^-1 (coarse_triangle.hpp: 64 x 64 blocks over bi >= bj,
+// factor's numbering, zero-padded), half the bytes.  y_f = T x_f with x_f[j] = b[perm[j]], x[perm[j]] = y_f[j] (perm: factor -> level).
+// tri_symv_items, one 256-thread workgroup per item (block row bi, at most kTriRun consecutive bj).  The item's x_f -- its own 64 rows and the
+// columns of its run -- is gathered through perm into LDS once, padding as zeros.  Wave w owns the 16-column strip [16 w, 16 w + 16) of every
+// block: lane = row group * 8 + column pair, a 16-byte load per lane covers 8 rows x 128 contiguous bytes per wave, 8 loads per lane and block
+// (rows rg + 8 k) -- every entry of T is read once; the next block's loads are issued before the current block's arithmetic.  A block B(bi, bj) feeds
+//   * the row part  y[bi 64 + i] += sum_j B[i][j] x[bj 64 + j]: per lane over the whole run (columns ascending), and once per item the 8 column
+//     pairs of a wave by an xor tree (1, 2, 4) and the four strips in wave order through LDS, into row scratch slot `item`;
+//   * below the diagonal the column part  y[bj 64 + j] += sum_i B[i][j] x[bi 64 + i]: per lane over its 8 rows (ascending), the 8 row groups of
+//     the wave by an xor tree (8, 16, 32) -- a strip's columns belong to one wave, no barrier -- into column scratch slot tri_block_offset(bi, bj).
+// tri_symv_reduce, one workgroup per output block b, then adds b's partials, listed in the order of coarse_triangle.hpp (row partials in run
+// order, then column partials in ascending bi): partial k goes to part k mod 4, a part adds its partials in ascending k, and the output is
+// ((part 0 + part 1) + part 2) + part 3; it is scattered through perm.  No atomics; the order of every sum is fixed by the indices alone, and
+// a column's sums never see the other columns: one column alone gives the bits of that column in a group.  Both scratch arrays are sized at
+// set-up for one group of kTriCols columns (the groups of a cycle run one after the other on the stream).
+// NT: non-temporal instead of plain loads of T (the measurement switch GMG_TRI_NT; scripts/coarse_triangle.py: plain loads are 2 - 3 us faster at n_L = 6 005).
+template <int D, bool NT>
+__global__ __launch_bounds__(kBlock) void tri_symv_items(const double* __restrict__ T, const int* __restrict__ perm, int n, const double* __restrict__ b, int ldv,
+                                                         double* __restrict__ rowp, double* __restrict__ colp) {
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    using namespace gmg;
+    static_assert(D <= kTriCols && kTriBlock == 64 && kBlock == 256 && kTriRun * kTriBlock <= kBlock, "one 64 x 64 block per four waves; a thread per column of the run");
+    constexpr int K = 8;                                   // rows of a block a lane holds: rg + 8 k
+    __shared__ __attribute__((aligned(16))) double xs[D][kTriRun * kTriBlock];      // x_f of the run's columns
+    __shared__ double xi[D][kTriBlock];                                            // x_f of the item's rows
+    __shared__ double rsum[kWavesPerBlock][D][kTriBlock];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, rg = lane >> 3, cp = lane & 7;
+    const TriItem it = tri_item(blockIdx.x);
+    const double* blk = T + tri_block_offset(it.bi, it.bj0) * kTriBlockDoubles + rg * kTriBlock + 16 * wave + 2 * cp;
+    auto load_block = [&](d2 (&v)[K], const double* src) {
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const d2* a = reinterpret_cast<const d2*>(src + 8 * k * kTriBlock);
+            v[k] = NT ? __builtin_nontemporal_load(a) : *a;
+        }
+    };
+    d2 v[K];
+    load_block(v, blk);
+    {
+        const int col = it.bj0 * kTriBlock + tid, row = it.bi * kTriBlock + tid;
+        const int pc = (tid < it.len * kTriBlock && col < n) ? perm[col] : -1;
+        const int pr = (tid < kTriBlock && row < n) ? perm[row] : -1;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            if (tid < kTriRun * kTriBlock) xs[c][tid] = pc >= 0 ? b[pc + (int64_t)c * ldv] : 0.0;
+            if (tid < kTriBlock) xi[c][tid] = pr >= 0 ? b[pr + (int64_t)c * ldv] : 0.0;
+        }
+    }
+    __syncthreads();
+    double racc[K][D];
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < D; ++c) racc[k][c] = 0.0;
+#pragma unroll 1
+    for (int q = 0; q < it.len; ++q) {                     // (not unrolled: the registers of one block and of the next one's loads, no more)
+        {
+            const int bj = it.bj0 + q;
+            d2 vn[K];
+            if (q + 1 < it.len) load_block(vn, blk + (int64_t)(q + 1) * kTriBlockDoubles);
+#pragma unroll
+            for (int c = 0; c < D; ++c) {
+                const d2 xj = *reinterpret_cast<const d2*>(&xs[c][q * kTriBlock + 16 * wave + 2 * cp]);
+#pragma unroll
+                for (int k = 0; k < K; ++k) { racc[k][c] += v[k].x * xj.x; racc[k][c] += v[k].y * xj.y; }
+            }
+            if (bj != it.bi) {
+#pragma unroll
+                for (int c = 0; c < D; ++c) {
+                    double c0 = 0.0, c1 = 0.0;
+#pragma unroll
+                    for (int k = 0; k < K; ++k) {
+                        const double xr = xi[c][rg + 8 * k];
+                        c0 += v[k].x * xr;
+                        c1 += v[k].y * xr;
+                    }
+#pragma unroll
+                    for (int off = 8; off < 64; off <<= 1) {      // a + b == b + a: every lane of a column pair ends with the same bits
+                        c0 += __shfl_xor(c0, off, 64);
+                        c1 += __shfl_xor(c1, off, 64);
+                    }
+                    if (rg == 0) {
+                        d2 s; s.x = c0; s.y = c1;
+                        *reinterpret_cast<d2*>(colp + (tri_block_offset(it.bi, bj) * kTriCols + c) * kTriBlock + 16 * wave + 2 * cp) = s;
+                    }
+                }
+            }
+            if (q + 1 < it.len) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) v[k] = vn[k];
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            double s = racc[k][c];
+#pragma unroll
+            for (int off = 1; off < 8; off <<= 1) s += __shfl_xor(s, off, 64);
+            if (cp == 0) rsum[wave][c][rg + 8 * k] = s;
+        }
+    __syncthreads();
+    if (tid < D * kTriBlock) {
+        const int c = tid >> 6;
+        double s = rsum[0][c][lane];
+#pragma unroll
+        for (int w = 1; w < kWavesPerBlock; ++w) s += rsum[w][c][lane];
+        rowp[((int64_t)blockIdx.x * kTriCols + c) * kTriBlock + lane] = s;
+    }
+}
+
+template <int D>
+__global__ __launch_bounds__(kBlock) void tri_symv_reduce(const double* __restrict__ rowp, const double* __restrict__ colp, const int* __restrict__ perm, int n,
+                                                          int nb, double* __restrict__ x, int ldv) {
+    using namespace gmg;
+    constexpr int U = 8;                                   // partials of a part requested together (their sum keeps the part's order)
+    constexpr int P = kWavesPerBlock;                      // parts: one wave each
+    __shared__ double part[P][D][kTriBlock];
+    const int p = threadIdx.x >> 6, i = threadIdx.x & 63, blk = blockIdx.x;
+    const int cnt = tri_partial_count(nb, blk);
+    auto at = [&](int k) {
+        bool col;
+        const int64_t slot = tri_partial_slot(blk, k, &col);
+        return (col ? colp : rowp) + slot * kTriCols * kTriBlock + i;
+    };
+    double s[D];
+#pragma unroll
+    for (int c = 0; c < D; ++c) s[c] = 0.0;
+    int k = p;
+    for (; k + P * (U - 1) < cnt; k += P * U) {
+        double v[U][D];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const double* a = at(k + P * u);
+#pragma unroll
+            for (int c = 0; c < D; ++c) v[u][c] = a[c * kTriBlock];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int c = 0; c < D; ++c) s[c] += v[u][c];
+    }
+    for (; k < cnt; k += P) {
+        const double* a = at(k);
+#pragma unroll
+        for (int c = 0; c < D; ++c) s[c] += a[c * kTriBlock];
+    }
+#pragma unroll
+    for (int c = 0; c < D; ++c) part[p][c][i] = s[c];
+    __syncthreads();
+    if (threadIdx.x < D * kTriBlock) {
+        const int c = threadIdx.x >> 6;
+        double t = part[0][c][i];
+#pragma unroll
+        for (int w = 1; w < P; ++w) t += part[w][c][i];
+        const int row = blk * kTriBlock + i;
+        if (row < n) x[perm[row] + (int64_t)c * ldv] = t;
+    }
 }
 
 }  // namespace gmgk

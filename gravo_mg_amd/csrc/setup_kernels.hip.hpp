@@ -7,6 +7,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "coarse_triangle.hpp"
 
 namespace gmgs {
 
@@ -763,7 +764,8 @@ __global__ __launch_bounds__(64) void rap_rows(const int* __restrict__ a_ptr, co
 // ---- dense inverse of the coarsest operator, built on the device from the host's sparse LDL^T factor --------------------------------
 // (multigrid_solver.cpp:1401 + :1075: the reference factors A_L once per solve() and back-substitutes once per cycle; GMG_COARSE_DEVICE_INVERSE
 // turns the per-cycle part into ONE dense symmetric matrix-vector product on the device -- no host round trip inside the cycle.)
-// X = A_L^-1 = P^T (L^-T D^-1 L^-1) P, stored in the FACTOR's numbering (the product kernel permutes the vectors): n right-hand sides e_c,
+// X = A_L^-1 = P^T (L^-T D^-1 L^-1) P, computed in the FACTOR's numbering (GMG_COARSE_DEVICE_TRIANGLE keeps it there -- its product permutes the vectors; GMG_COARSE_DEVICE_INVERSE
+// moves it into the level's afterwards): n right-hand sides e_c,
 // every one an independent pair of sparse triangular solves.  One workgroup owns a TILE of 64 columns c (one lane per column: a row of X
 // restricted to the tile is 512 contiguous bytes) and carries it through the whole factor:
 //   * down (L y = e_c): y is nonzero only at ancestors of c in the elimination tree, so only chunks whose subtree meets the tile are visited
@@ -953,6 +955,24 @@ __global__ __launch_bounds__(256) void mirror_lower_to_upper(double* __restrict_
         const int row = bj * 64 + r, col = bc * 64 + tx;   // X[row][col] = X[col][row] = t[tx][r]
         if (row < n && col < n && row < col) X[(int64_t)row * n + col] = t[tx][r];
     }
+}
+
+// GMG_COARSE_DEVICE_TRIANGLE: the lower triangle of X (rows j >= c as the tiles left them) into the block layout of coarse_triangle.hpp, factor's
+// numbering kept: T[tri_block_offset(bi, bj)] = the 64 x 64 block (bi, bj), row-major, rows and columns beyond n zero.  A block on the diagonal
+// takes entry (j, c) from X[max(j, c)][min(j, c)] -- the rule of mirror_lower_to_upper, so T holds the bits the full matrix would.  Through LDS:
+// both sides coalesced.  grid: (nb, nb), nb = ceil(n / 64); blocks above the diagonal return.
+__global__ __launch_bounds__(256) void pack_lower_blocks(const double* __restrict__ X, int n, double* __restrict__ T) {
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj > bi) return;
+    __shared__ double t[64][65];
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int r = ty; r < 64; r += 4) {
+        const int row = bi * 64 + r, col = bj * 64 + tx;
+        t[r][tx] = (row < n && col < n) ? X[(int64_t)row * n + col] : 0.0;
+    }
+    __syncthreads();
+    double* out = T + gmg::tri_block_offset(bi, bj) * gmg::kTriBlockDoubles;
+    for (int r = ty; r < 64; r += 4) out[r * 64 + tx] = (bi == bj && r < tx) ? t[tx][r] : t[r][tx];
 }
 
 // out[perm[j]][perm[c]] = X[j][c]: the inverse from the factor's numbering into the level's (perm: factor -> level, inv its inverse), one

@@ -57,7 +57,7 @@ def main(args):
     else:
         dist.init_process_group(backend, rank=rank, world_size=world)
     assert world == args.gpus or args.gpus <= 1, f"--gpus {args.gpus} but WORLD_SIZE={world}"
-    coarse_mode = {"auto": cabi.COARSE_AUTO, "host": cabi.COARSE_HOST_LDLT, "device": cabi.COARSE_DEVICE_INVERSE}[args.coarse]
+    coarse_mode = {"auto": cabi.COARSE_AUTO, "host": cabi.COARSE_HOST_LDLT, "device": cabi.COARSE_DEVICE_INVERSE, "triangle": cabi.COARSE_DEVICE_TRIANGLE}[args.coarse]
 
     grow = world ** 0.5 if args.scaling == "weak" else 1.0                         # weak: n1 x n2 vertices per rank, same aspect ratio
     n1, n2 = int(round(args.n1 * grow)), int(round(args.n2 * grow))

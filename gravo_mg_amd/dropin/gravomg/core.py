@@ -301,7 +301,9 @@ class MultigridSolver(object):
         """MI355X engine knobs (not upstream): smoother (0 multicolour Gauss-Seidel, 1 weighted Jacobi, 2 Chebyshev polynomial on D^-1 A over
         its Gershgorin bound: pre / post iterations are then the polynomial degrees, one launch per step on every level, convergent for every symmetric positive definite system;
         gs_omega, jacobi_omega and block_* are without effect, gmg_config::smoother), gs_omega, jacobi_omega,
-        coarse_mode (0 host LDL^T back-substitution per cycle, 1 dense inverse built and applied on the device, 2 = default: 1 while the coarsest level has <= 8 192 unknowns -- a system solved ONCE is faster with 0), use_graph, block_rows, block_from_level, device,
+        coarse_mode (0 host LDL^T back-substitution per cycle, 1 dense inverse built and applied on the device, 2 = default: 1 while the coarsest level has <= 8 192 unknowns -- a system solved ONCE is faster with 0, DESIGN.md 4.5;
+        3 the packed lower triangle of that inverse, applied on the device at any size: half the resident bytes and half the bytes per application against a second,
+        small reduction launch -- GMG_COARSE_DEVICE_TRIANGLE), use_graph, block_rows, block_from_level, device,
         accelerate (0 = default: the reference's solve loop; m in 1..4: truncated GCR around the V-cycle -- each cycle's step is orthogonalised against the last m - 1 and scaled so
         that the tested residue is minimal and cannot grow; fp64 and one device only, gmg_config::accelerate)."""
         self.solver.set_engine_option(str(key), float(value))

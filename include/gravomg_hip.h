@@ -48,8 +48,13 @@ enum { GMG_SMOOTHER_MULTICOLOR_GS = 0, GMG_SMOOTHER_JACOBI = 1, GMG_SMOOTHER_CHE
 /* where the coarsest direct solve (multigrid_solver.cpp:1075) is applied.  HOST_LDLT: back-substitution with the host's supernodal factor, one
  * device -> host -> device round trip per cycle.  DEVICE_INVERSE: one dense symmetric matrix-vector product with A_L^-1 on the device; the inverse
  * is built on the device from the host's factor at gmg_set_system (timing keys "coarse_inverse_ms").  AUTO (default): DEVICE_INVERSE while the
- * coarsest level has at most 8 192 unknowns (the reference's lower_bound = 1000, ratio = 8 keep it below 8 000), else HOST_LDLT. */
-enum { GMG_COARSE_HOST_LDLT = 0, GMG_COARSE_DEVICE_INVERSE = 1, GMG_COARSE_AUTO = 2 };
+ * coarsest level has at most 8 192 unknowns (the reference's lower_bound = 1000, ratio = 8 keep it below 8 000), else HOST_LDLT.
+ * DEVICE_TRIANGLE: forced like DEVICE_INVERSE at whatever size, but only the packed lower triangle of A_L^-1 is kept (64 x 64 blocks in the
+ * factor's numbering; the product gathers and scatters through the factor's permutation): half the resident bytes and half the bytes per
+ * application, against a second, small reduction launch per group of 4 columns; deterministic, no atomics.  Measured (profiles/coarse_triangle):
+ * it pays from n_L of about 4 000 on -- per application 57 -> 47 us at n_L = 6 005 with three right-hand sides and 48 -> 33 us with one, 31 -> 30 us
+ * at 4 046; below that the second launch costs more than the bytes save (2 968: 16 -> 18 us, 1 929: 12 -> 16 us).  AUTO never picks it.  Timing keys "coarse_triangle", "coarse_inverse_bytes", "coarse_triangle_run_blocks". */
+enum { GMG_COARSE_HOST_LDLT = 0, GMG_COARSE_DEVICE_INVERSE = 1, GMG_COARSE_AUTO = 2, GMG_COARSE_DEVICE_TRIANGLE = 3 };
 
 typedef struct {
     int device;            /* HIP device ordinal */
@@ -66,7 +71,8 @@ typedef struct {
     double jacobi_omega;   /* damping for GMG_SMOOTHER_JACOBI (default 0.67) */
     int pre_iters;         /* MultigridSolver::preIters  (gravomg_bindings/src/cpp/core.cpp:55) */
     int post_iters;        /* MultigridSolver::postIters (core.cpp:56) */
-    int coarse_mode;       /* GMG_COARSE_*: where the coarsest direct solve is applied (default GMG_COARSE_AUTO) */
+    int coarse_mode;       /* GMG_COARSE_*: where the coarsest direct solve is applied (default GMG_COARSE_AUTO; GMG_COARSE_DEVICE_TRIANGLE = 3: on the device from
+                              the packed lower triangle of the inverse -- half the memory and bytes, one more launch); other values: the host */
     int use_graph;         /* 1: replay the V-cycle legs from captured hipGraphs; 0 (default): plain stream launches */
     int sigma;             /* length-sorting window (rows) inside the colour classes of a colour-major level (multiple of 64; 0 = no sorting,
                               the default: sorting rows by length trades SELL padding for locality of the gathers, and on the irregular
