@@ -196,7 +196,7 @@ void gmg_destroy(gmg_handle h) {
         p2p_release_handle(h);
         drop_system(h);
         drop_device_transfers(h);
-        for (double** p : {&h->d_stage, &h->d_partials, &h->d_norm, &h->d_watch}) if (*p) (void)dev_free(*p);
+        h->d_stage = {}; h->d_partials = {}; h->d_norm = {}; h->d_watch = {};       // (every pool block is parked before the pool is emptied and the handle deleted)
         if (h->h_pinned) (void)sync_hipHostFree(h->h_pinned);
         for (int i = 0; i < 2; ++i) { if (h->h_stage[i]) (void)sync_hipHostFree(h->h_stage[i]); if (h->h_stage_ev[i]) (void)hipEventDestroy(h->h_stage_ev[i]); }
         for (hipEvent_t& e : h->h_chunk_ev) if (e) (void)hipEventDestroy(e);
@@ -431,6 +431,7 @@ int gmg_debug_col16_copy(gmg_handle h, int which, int64_t* info, unsigned* col16
 int gmg_get_timing(gmg_handle h, const char* key, double* out) try {
     if (!h || !key || !out) return GMG_ERR_INVALID;
     if (std::string(key) == "device_bytes_now") { *out = (double)h->pool.live_bytes; return GMG_OK; }      // device memory the handle holds at this moment (pool blocks in use)
+    if (std::string(key) == "device_blocks_now") { *out = (double)(h->pool.size_of.size() - h->pool.parked.size()); return GMG_OK; }      // ... and how many blocks that is
     if (std::string(key) == "restrict_sweeps_fused") { *out = (double)h->fused_restrictions; return GMG_OK; }      // fused restriction + first pre-sweep launches enqueued so far (gmg_config::fuse_restrict_sweep)
     auto it = h->timing.find(key);
     if (it == h->timing.end()) return fail(h, GMG_ERR_INVALID, std::string("unknown timing key: ") + key);
@@ -844,12 +845,12 @@ int gmg_set_system_values_device(gmg_handle h, const double* d_val, int64_t nnz)
     HIPCHK(hipSetDevice(h->cfg.device));
     if (l0.ord.blocked && h->cfg.block_from_level >= 1) {
         // a level 0 that gmg_config::block_fine blocked stays blocked only while the new values pass its sign test (values_only does the same on the host)
-        DevTmp<int> d_bad;
-        if ((rc = d_bad.alloc(h, 1))) return rc;
+        DevBuf<int> d_bad;
+        if ((rc = dev_alloc(h, d_bad, 1))) return rc;
         int bad = 0;
-        HIPCHK(hipMemsetAsync(d_bad.p, 0, sizeof(int), h->stream));
-        hipLaunchKernelGGL(gmgk::stieltjes_signs_flag, dim3((l0.n + 255) / 256), dim3(256), 0, h->stream, l0.n, l0.dA.ptr, l0.dA.idx, d_val, d_bad.p);
-        HIPCHK(hipMemcpyAsync(&bad, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemsetAsync(d_bad, 0, sizeof(int), h->stream));
+        hipLaunchKernelGGL(gmgk::stieltjes_signs_flag, dim3((l0.n + 255) / 256), dim3(256), 0, h->stream, l0.n, l0.dA.ptr.get(), l0.dA.idx.get(), d_val, d_bad.get());
+        HIPCHK(hipMemcpyAsync(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (bad) return fail(h, GMG_ERR_STATE, "these values fail the sign test of the blocked level 0 (gmg_config::block_fine: positive diagonal, no positive off-diagonal entry): this system needs a full set-up through gmg_set_system");
     }
@@ -915,8 +916,8 @@ int gmg_dist_bind(gmg_handle h, double* x0, double* b0, double* r0, int d) try {
     if (rc) return rc;
     drop_graphs(h);
     Level& l = h->lv[0];
-    if (!h->bound) { h->own_x0 = l.x; h->own_b0 = l.b; h->own_r0 = l.r; }
-    l.x = x0; l.b = b0; l.r = r0;
+    if (!l.x.borrowed()) { h->own_x0 = std::move(l.x); h->own_b0 = std::move(l.b); h->own_r0 = std::move(l.r); }      // the engine's vectors are parked ...
+    l.x.borrow(x0); l.b.borrow(b0); l.r.borrow(r0);                                                                        // ... the caller's stay the caller's
     h->bound = true;
     h->loaded_d = d;
     return GMG_OK;
@@ -1391,9 +1392,9 @@ int gmg_set_fine_order(gmg_handle h, int n, const int* order) try {
             seen[order[i]] = 1;
         }
     }
+    PoolScope pool_scope_(&h->pool);
     h->bfs_order.assign(order, order + n);
-    if (h->d_bfs_order) { (void)dev_free(h->d_bfs_order); h->d_bfs_order = nullptr; }
-    if (h->d_bfs_inv) { (void)dev_free(h->d_bfs_inv); h->d_bfs_inv = nullptr; }
+    h->d_bfs_order = {}; h->d_bfs_inv = {};
     h->ord_cache_valid = false;        // cached orderings were built on another base order
     return GMG_OK;
 } GMG_CATCH_H

@@ -535,23 +535,21 @@ int ensure_vectors(gmg_handle h, int d) {
     if (d <= h->dcap) return GMG_OK;
     drop_graphs(h);
     unbind_level0(h);
-    drop_accel(h);
+    h->accel = {};
+    // a zeroed n_pad x d vector of the level, or none (wanted = false): the old one goes back to the pool either way
+    auto vec = [&](auto& v, const Level& l, bool wanted) -> int {
+        v.reset();
+        if (!wanted) return GMG_OK;
+        const size_t count = (size_t)l.n_pad * d;
+        int rc = dev_alloc(h, v, count);
+        if (rc == GMG_OK) HIPCHK(hipMemsetAsync(v, 0, sizeof(*v.get()) * count, h->stream));
+        return rc;
+    };
     for (auto& l : h->lv) {
-        for (double** p : {&l.x, &l.b, &l.r, &l.tmp}) {
-            if (*p) { (void)dev_free(*p); *p = nullptr; }
-            if (p == &l.tmp && !pointwise_smoother(h->cfg) && !l.ord.blocked) continue;
-            size_t bytes = sizeof(double) * (size_t)l.n_pad * d;
-            HIPCHK(dev_malloc((void**)p, bytes));
-            HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));
-        }
-        for (float** p : {&l.x32, &l.b32, &l.r32, &l.tmp32}) {
-            if (*p) { (void)dev_free(*p); *p = nullptr; }
-            if (!h->cfg.inner_precision) continue;
-            if (p == &l.tmp32 && !pointwise_smoother(h->cfg) && !l.ord.blocked) continue;
-            size_t bytes = sizeof(float) * (size_t)l.n_pad * d;
-            HIPCHK(dev_malloc((void**)p, bytes));
-            HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));
-        }
+        const bool tmp = pointwise_smoother(h->cfg) || l.ord.blocked, f32 = h->cfg.inner_precision != 0;
+        int rc;
+        if ((rc = vec(l.x, l, true)) || (rc = vec(l.b, l, true)) || (rc = vec(l.r, l, true)) || (rc = vec(l.tmp, l, tmp)) ||
+            (rc = vec(l.x32, l, f32)) || (rc = vec(l.b32, l, f32)) || (rc = vec(l.r32, l, f32)) || (rc = vec(l.tmp32, l, f32 && tmp))) return rc;
     }
     Level& c = h->lv[h->L];
     size_t need = (size_t)c.n_pad * d * 2;
@@ -567,10 +565,10 @@ int ensure_vectors(gmg_handle h, int d) {
         std::memset(h->h_flag, 0, 256);
     }
 
-    if (h->d_norm) (void)dev_free(h->d_norm);
-    HIPCHK(dev_malloc((void**)&h->d_norm, sizeof(double) * 2 * d));
+    int rc;
+    if ((rc = dev_alloc(h, h->d_norm, (size_t)2 * d))) return rc;
     if (!h->d_watch) {
-        HIPCHK(dev_malloc((void**)&h->d_watch, 16));
+        if ((rc = dev_alloc(h, h->d_watch, 2))) return rc;
         HIPCHK(hipMemsetAsync(h->d_watch, 0, 16, h->stream));
     }
     h->dcap = d;
@@ -580,8 +578,8 @@ int ensure_vectors(gmg_handle h, int d) {
 
 int ensure_stage(gmg_handle h, size_t n_doubles) {
     if (n_doubles <= h->stage_cap) return GMG_OK;
-    if (h->d_stage) (void)dev_free(h->d_stage);
-    HIPCHK(dev_malloc((void**)&h->d_stage, sizeof(double) * n_doubles));
+    int rc;
+    if ((rc = dev_alloc(h, h->d_stage, n_doubles))) return rc;
     h->stage_cap = n_doubles;
     return GMG_OK;
 }
@@ -1093,18 +1091,18 @@ int ensure_accel(gmg_handle h) {
     auto& a = h->accel;
     const int m = h->cfg.accelerate, n_pad = h->lv[0].n_pad, D = h->dcap;
     if (a.xk && a.depth == m && a.d == D && a.n_pad == n_pad) return GMG_OK;
-    drop_accel(h);
-    const size_t bytes = sizeof(double) * (size_t)n_pad * D;
-    auto vec = [&](double** p) -> int {
-        HIPCHK(dev_malloc((void**)p, bytes));
-        HIPCHK(hipMemsetAsync(*p, 0, bytes, h->stream));          // (padding rows: zero, and no kernel writes anything else there)
-        return GMG_OK;
+    a = {};
+    const size_t count = (size_t)n_pad * D;
+    auto vec = [&](DevBuf<double>* p) -> int {
+        int rc = dev_alloc(h, *p, count);
+        if (rc == GMG_OK) HIPCHK(hipMemsetAsync(*p, 0, sizeof(double) * count, h->stream));          // (padding rows: zero, and no kernel writes anything else there)
+        return rc;
     };
     int rc;
-    for (double** p : {&a.xk, &a.r, &a.z0}) if ((rc = vec(p))) return rc;
-    for (int j = 0; j < m - 1; ++j) for (double** p : {&a.zs[j], &a.qs[j]}) if ((rc = vec(p))) return rc;
-    HIPCHK(dev_malloc((void**)&a.scal, sizeof(double) * ((size_t)9 * D + 1)));          // alpha, guarded, 3 betas, 3 s_j per column; guard_steps; <b, b> per column
-    HIPCHK(dev_malloc((void**)&a.partials, sizeof(double) * (size_t)gmgk::kAccelMaxBlocks * gmgk::kAccelMaxComp));
+    for (DevBuf<double>* p : {&a.xk, &a.r, &a.z0}) if ((rc = vec(p))) return rc;
+    for (int j = 0; j < m - 1; ++j) for (DevBuf<double>* p : {&a.zs[j], &a.qs[j]}) if ((rc = vec(p))) return rc;
+    if ((rc = dev_alloc(h, a.scal, (size_t)9 * D + 1)) ||          // alpha, guarded, 3 betas, 3 s_j per column; guard_steps; <b, b> per column
+        (rc = dev_alloc(h, a.partials, (size_t)gmgk::kAccelMaxBlocks * gmgk::kAccelMaxComp))) return rc;
     a.depth = m; a.d = D; a.n_pad = n_pad;
     return GMG_OK;
 }

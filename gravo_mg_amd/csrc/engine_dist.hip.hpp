@@ -742,9 +742,8 @@ int gmg_p2p_load(gmg_handle h, const double* b, const double* x0) try {
     HIPCHK(hipMemsetAsync(p->d_err, 0, sizeof(int), h->stream));
     int rc = gmg_load_problem(h, b, x0, p->d);
     if (rc) return rc;
-    // the distributed steps address the level-0 vectors through the `bound` state of the gmg_dist_* entry points
-    Level& l = h->lv[0];
-    h->own_x0 = l.x; h->own_b0 = l.b; h->own_r0 = l.r;
+    // the distributed steps address the level-0 vectors through the `bound` state of the gmg_dist_* entry points: bound to the level's own
+    // vectors, which stay where they are (nothing parked: unbind_level0 has nothing to move back)
     h->bound = true;
     return GMG_OK;
 } GMG_CATCH_H

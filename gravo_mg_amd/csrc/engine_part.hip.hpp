@@ -140,22 +140,20 @@ int build_dist_plan(gmg_handle h, DistPlan& P, int rank, int world, const Patter
 }
 
 // Masked row maps of a partitioned set-up: new2old of level 0 / level 1 with -1 for the rows of other ranks (gmgs::mask_rows_*).
-int make_row_masks(gmg_handle h, const DistPlan& P, int** d_mask0, int** d_mask1) {
+int make_row_masks(gmg_handle h, const DistPlan& P, DevBuf<int>& d_mask0, DevBuf<int>& d_mask1) {
     Level& l0 = h->lv[0];
     const LevelOrdering& o = l0.ord;
-    DevTmp<int> d_cb;
+    DevBuf<int> d_cb;
     int rc;
-    if ((rc = d_cb.alloc(h, (size_t)dist_classes(o) + 1))) return rc;
-    HIPCHK(hipMemcpyAsync(d_cb.p, o.color_begin.data(), sizeof(int) * ((size_t)dist_classes(o) + 1), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(dev_malloc((void**)d_mask0, sizeof(int) * (size_t)l0.n_pad));
-    hipLaunchKernelGGL(gmgs::mask_rows_by_colour, dim3((l0.n_pad + 255) / 256), dim3(256), 0, h->stream, l0.d_new2old, l0.n_pad, d_cb.p, dist_classes(o), P.world, P.rank, *d_mask0);
+    if ((rc = dev_alloc(h, d_cb, (size_t)dist_classes(o) + 1)) || (rc = dev_alloc(h, d_mask0, (size_t)l0.n_pad))) return rc;
+    HIPCHK(hipMemcpyAsync(d_cb, o.color_begin.data(), sizeof(int) * ((size_t)dist_classes(o) + 1), hipMemcpyHostToDevice, h->stream));
+    hipLaunchKernelGGL(gmgs::mask_rows_by_colour, dim3((l0.n_pad + 255) / 256), dim3(256), 0, h->stream, l0.d_new2old.get(), l0.n_pad, d_cb.get(), dist_classes(o), P.world, P.rank, d_mask0.get());
     if (P.shard1) {
         Level& l1 = h->lv[1];
-        DevTmp<int> d_own;
-        if ((rc = d_own.alloc(h, P.blk_owner.size()))) return rc;
-        HIPCHK(hipMemcpyAsync(d_own.p, P.blk_owner.data(), sizeof(int) * P.blk_owner.size(), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(dev_malloc((void**)d_mask1, sizeof(int) * (size_t)l1.n_pad));
-        hipLaunchKernelGGL(gmgs::mask_rows_by_block, dim3((l1.n_pad + 255) / 256), dim3(256), 0, h->stream, l1.d_new2old, l1.n_pad, d_own.p, P.rank, *d_mask1);
+        DevBuf<int> d_own;
+        if ((rc = dev_alloc(h, d_own, P.blk_owner.size())) || (rc = dev_alloc(h, d_mask1, (size_t)l1.n_pad))) return rc;
+        HIPCHK(hipMemcpyAsync(d_own, P.blk_owner.data(), sizeof(int) * P.blk_owner.size(), hipMemcpyHostToDevice, h->stream));
+        hipLaunchKernelGGL(gmgs::mask_rows_by_block, dim3((l1.n_pad + 255) / 256), dim3(256), 0, h->stream, l1.d_new2old.get(), l1.n_pad, d_own.get(), P.rank, d_mask1.get());
         HIPCHK(hipStreamSynchronize(h->stream));      // (the small host arrays above are pageable; d_own / d_cb die at scope end)
     } else HIPCHK(hipStreamSynchronize(h->stream));
     return GMG_OK;

@@ -6,44 +6,35 @@ namespace {
 
 // ---- device-side layout construction (setup_kernels.hip.hpp) ------------------------------------------------
 int upload_csr(gmg_handle h, DevCsr& d, const Compressed& m) {
-    free_csr(d);
+    d = {};
     d.n_outer = m.n_outer;
     int rc;
-    if ((rc = upload(h, &d.ptr, m.ptr)) || (rc = upload(h, &d.idx, m.idx)) || (rc = upload(h, &d.val, m.val))) return rc;
+    if ((rc = upload(h, d.ptr, m.ptr)) || (rc = upload(h, d.idx, m.idx)) || (rc = upload(h, d.val, m.val))) return rc;
     return GMG_OK;
 }
 
 int upload_csr_raw(gmg_handle h, DevCsr& d, int n_outer, const int* ptr, const int* idx, const double* val) {
-    free_csr(d);
+    d = {};
     d.n_outer = n_outer;
     const size_t nnz = (size_t)ptr[n_outer];
-    HIPCHK(dev_malloc((void**)&d.ptr, sizeof(int) * ((size_t)n_outer + 1)));
-    HIPCHK(dev_malloc((void**)&d.idx, sizeof(int) * std::max<size_t>(nnz, 1)));
-    HIPCHK(dev_malloc((void**)&d.val, sizeof(double) * std::max<size_t>(nnz, 1)));
     int rc;
+    if ((rc = dev_alloc(h, d.ptr, (size_t)n_outer + 1)) || (rc = dev_alloc(h, d.idx, nnz)) || (rc = dev_alloc(h, d.val, nnz))) return rc;
     if ((rc = h2d(h, d.ptr, ptr, sizeof(int) * ((size_t)n_outer + 1))) || (rc = h2d(h, d.idx, idx, sizeof(int) * nnz)) || (rc = h2d(h, d.val, val, sizeof(double) * nnz))) return rc;
     return GMG_OK;
 }
-
-template <class T>
-struct DevTmp {                       // scratch device array released at scope exit (stream-ordered reuse through the pool)
-    T* p = nullptr;
-    ~DevTmp() { if (p) (void)dev_free(p); }
-    int alloc(gmg_handle h, size_t n) { HIPCHK(dev_malloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T))); return GMG_OK; }
-};
 
 // out[0..n] = exclusive prefix sums of in[0..n) on the stream; *total_host (pinned or pageable) receives out[n] after
 // the caller synchronises.
 template <class TIn, class TOut>
 int device_scan(gmg_handle h, const TIn* in, int n, TOut* out, TOut* total_host) {
     const int tiles = std::max(1, (n + gmgs::kScanTile - 1) / gmgs::kScanTile);
-    DevTmp<TOut> tile;
+    DevBuf<TOut> tile;          // (scratch: back to the pool at scope exit, reused in stream order)
     int rc;
-    if ((rc = tile.alloc(h, (size_t)tiles + 1))) return rc;
-    hipLaunchKernelGGL((gmgs::scan_tile_sums<TIn, TOut>), dim3(tiles), dim3(256), 0, h->stream, in, n, tile.p);
-    hipLaunchKernelGGL((gmgs::scan_tile_offsets<TOut>), dim3(1), dim3(1024), 0, h->stream, tile.p, tiles, tile.p + tiles);
-    hipLaunchKernelGGL((gmgs::scan_tile_apply<TIn, TOut>), dim3(tiles), dim3(256), 0, h->stream, in, n, (const TOut*)tile.p, out);
-    if (total_host) HIPCHK(hipMemcpyAsync(total_host, tile.p + tiles, sizeof(TOut), hipMemcpyDeviceToHost, h->stream));
+    if ((rc = dev_alloc(h, tile, (size_t)tiles + 1))) return rc;
+    hipLaunchKernelGGL((gmgs::scan_tile_sums<TIn, TOut>), dim3(tiles), dim3(256), 0, h->stream, in, n, tile.get());
+    hipLaunchKernelGGL((gmgs::scan_tile_offsets<TOut>), dim3(1), dim3(1024), 0, h->stream, tile.get(), tiles, tile + tiles);
+    hipLaunchKernelGGL((gmgs::scan_tile_apply<TIn, TOut>), dim3(tiles), dim3(256), 0, h->stream, in, n, (const TOut*)tile, out);
+    if (total_host) HIPCHK(hipMemcpyAsync(total_host, tile + tiles, sizeof(TOut), hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
 }
 
@@ -52,13 +43,13 @@ int device_scan(gmg_handle h, const TIn* in, int n, TOut* out, TOut* total_host)
 // col16: write 16-bit columns into *col16_out (in-block part of a blocked level) instead of out.col.
 // src_out / diag_src_out (optional, first build only): allocate and fill the source maps of the layout (gmgs::sell_fill's `src` / `diag_src`)
 int device_build_sell(gmg_handle h, DevSell& out, const int* pbeg, const int* pend, const int* idx, const double* val, gmgs::RowFilter f,
-                      const int* d_order, int n_rows_pad, int lpr, unsigned short** col16_out, double* d_diag, int* d_err, bool refill = false,
-                      int** src_out = nullptr, int** diag_src_out = nullptr) {
+                      const int* d_order, int n_rows_pad, int lpr, DevBuf<unsigned short>* col16_out, double* d_diag, int* d_err, bool refill = false,
+                      DevBuf<int>* src_out = nullptr, DevBuf<int>* diag_src_out = nullptr) {
     auto fill = [&]() {
         const dim3 grid((n_rows_pad + 255) / 256);
-        int* src = src_out ? *src_out : nullptr;
-        int* dsrc = diag_src_out ? *diag_src_out : nullptr;
-        if (col16_out) hipLaunchKernelGGL(gmgs::sell_fill<unsigned short>, grid, dim3(256), 0, h->stream, pbeg, pend, idx, val, f, d_order, lpr, n_rows_pad, out.slice_ptr, *col16_out, out.val, d_diag, d_err, src, dsrc);
+        int* src = src_out ? src_out->get() : nullptr;
+        int* dsrc = diag_src_out ? diag_src_out->get() : nullptr;
+        if (col16_out) hipLaunchKernelGGL(gmgs::sell_fill<unsigned short>, grid, dim3(256), 0, h->stream, pbeg, pend, idx, val, f, d_order, lpr, n_rows_pad, out.slice_ptr, col16_out->get(), out.val, d_diag, d_err, src, dsrc);
         else hipLaunchKernelGGL(gmgs::sell_fill<int>, grid, dim3(256), 0, h->stream, pbeg, pend, idx, val, f, d_order, lpr, n_rows_pad, out.slice_ptr, out.col, out.val, d_diag, d_err, src, dsrc);
     };
     if (refill) {        // same pattern as the matrix this layout was built from: slice pointers stand, entries are rewritten
@@ -66,38 +57,32 @@ int device_build_sell(gmg_handle h, DevSell& out, const int* pbeg, const int* pe
         fill();
         return GMG_OK;
     }
-    free_sell(out);
+    out = {};
     const int rps = 64 / lpr;
     out.lpr = lpr;
     out.n_slices = n_rows_pad / rps;
-    DevTmp<int> len;
-    DevTmp<int64_t> widths;
+    DevBuf<int> len;
+    DevBuf<int64_t> widths;
     int rc;
-    if ((rc = len.alloc(h, n_rows_pad)) || (rc = widths.alloc(h, out.n_slices))) return rc;
-    HIPCHK(dev_malloc((void**)&out.slice_ptr, sizeof(int64_t) * ((size_t)out.n_slices + 1)));
-    hipLaunchKernelGGL(gmgs::row_lengths, dim3((n_rows_pad + 255) / 256), dim3(256), 0, h->stream, pbeg, pend, idx, f, d_order, n_rows_pad, len.p, d_err);
-    hipLaunchKernelGGL(gmgs::slice_widths, dim3((out.n_slices + 255) / 256), dim3(256), 0, h->stream, len.p, lpr, out.n_slices, widths.p);
+    if ((rc = dev_alloc(h, len, n_rows_pad)) || (rc = dev_alloc(h, widths, out.n_slices)) || (rc = dev_alloc(h, out.slice_ptr, (size_t)out.n_slices + 1))) return rc;
+    hipLaunchKernelGGL(gmgs::row_lengths, dim3((n_rows_pad + 255) / 256), dim3(256), 0, h->stream, pbeg, pend, idx, f, d_order, n_rows_pad, len.get(), d_err);
+    hipLaunchKernelGGL(gmgs::slice_widths, dim3((out.n_slices + 255) / 256), dim3(256), 0, h->stream, len.get(), lpr, out.n_slices, widths.get());
     int64_t total = 0;
-    if ((rc = device_scan<int64_t, int64_t>(h, widths.p, out.n_slices, out.slice_ptr, &total))) return rc;
+    if ((rc = device_scan<int64_t, int64_t>(h, widths, out.n_slices, out.slice_ptr, &total))) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     out.stored = total;
-    HIPCHK(dev_malloc((void**)&out.val, std::max<int64_t>(out.stored, 1) * sizeof(double)));
-    if (col16_out) {
-        if (*col16_out) { (void)dev_free(*col16_out); *col16_out = nullptr; }
-        HIPCHK(dev_malloc((void**)col16_out, std::max<int64_t>(out.stored, 1) * sizeof(unsigned short)));
-    } else HIPCHK(dev_malloc((void**)&out.col, std::max<int64_t>(out.stored, 1) * sizeof(int)));
-    if (src_out) { if (*src_out) { (void)dev_free(*src_out); *src_out = nullptr; } HIPCHK(dev_malloc((void**)src_out, std::max<int64_t>(out.stored, 1) * sizeof(int))); }
-    if (diag_src_out) { if (*diag_src_out) { (void)dev_free(*diag_src_out); *diag_src_out = nullptr; } HIPCHK(dev_malloc((void**)diag_src_out, (size_t)std::max(n_rows_pad, 1) * sizeof(int))); }
+    if ((rc = dev_alloc(h, out.val, (size_t)out.stored)) || (rc = col16_out ? dev_alloc(h, *col16_out, (size_t)out.stored) : dev_alloc(h, out.col, (size_t)out.stored))) return rc;
+    if (src_out && (rc = dev_alloc(h, *src_out, (size_t)out.stored))) return rc;
+    if (diag_src_out && (rc = dev_alloc(h, *diag_src_out, (size_t)n_rows_pad))) return rc;
     fill();
     return GMG_OK;
 }
 
 int build_ell3(gmg_handle h, DevEll3& e, const DevCsr& dU, int n_fine, int* d_err) {
-    free_ell3(e);
+    e = {};
     e.n = n_fine;
-    HIPCHK(dev_malloc((void**)&e.cnt, sizeof(int) * std::max(n_fine, 1)));
-    HIPCHK(dev_malloc((void**)&e.col, sizeof(int) * (size_t)std::max(n_fine, 1) * 3));
-    HIPCHK(dev_malloc((void**)&e.val, sizeof(double) * (size_t)std::max(n_fine, 1) * 3));
+    int rc;
+    if ((rc = dev_alloc(h, e.cnt, (size_t)n_fine)) || (rc = dev_alloc(h, e.col, (size_t)std::max(n_fine, 1) * 3)) || (rc = dev_alloc(h, e.val, (size_t)std::max(n_fine, 1) * 3))) return rc;
     HIPCHK(hipMemsetAsync(e.cnt, 0, sizeof(int) * n_fine, h->stream));
     hipLaunchKernelGGL(gmgs::ell3_from_csc, dim3((dU.n_outer + 255) / 256), dim3(256), 0, h->stream, dU.ptr, dU.idx, dU.val, dU.n_outer, e.cnt, e.col, e.val, d_err);
     hipLaunchKernelGGL(gmgs::ell3_sort, dim3((n_fine + 255) / 256), dim3(256), 0, h->stream, e.cnt, n_fine, e.col, e.val);
@@ -112,20 +97,20 @@ int ensure_device_transfers(gmg_handle h) {
     if (complete) return GMG_OK;
     if (!h->dU_ready || (int)h->dU.size() != L) {
         drop_device_transfers(h);
-        h->dU.assign(L, DevCsr());
-        h->dE3.assign(L, DevEll3());
+        h->dU.resize(L);
+        h->dE3.resize(L);
     }
-    DevTmp<int> d_err;
+    DevBuf<int> d_err;
     int rc, herr = 0;
-    if ((rc = d_err.alloc(h, 1))) return rc;
-    HIPCHK(hipMemsetAsync(d_err.p, 0, sizeof(int), h->stream));
+    if ((rc = dev_alloc(h, d_err, 1))) return rc;
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->stream));
     for (int k = 0; k < L; ++k) {
         if (h->dU[k].ptr) continue;
         rc = upload_csr(h, h->dU[k], h->U[k]);
-        if (rc == GMG_OK) rc = build_ell3(h, h->dE3[k], h->dU[k], h->U[k].n_inner, d_err.p);
+        if (rc == GMG_OK) rc = build_ell3(h, h->dE3[k], h->dU[k], h->U[k].n_inner, d_err);
         if (rc) return rc;
     }
-    HIPCHK(hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));      // pageable host arrays have been consumed
     h->dU_flagged = h->dU_flagged || herr != 0;      // a U row with more than 3 entries: the device RAP / layout builder cannot take it
     h->dU_ready = true;
@@ -135,8 +120,8 @@ int ensure_device_transfers(gmg_handle h) {
 // The base order of a reordered level 0 in use (gmg_set_system decides per system, choose_base_order): new -> old.
 inline const std::vector<int>& base_order(gmg_handle h) { return h->base_order_choice == 1 ? h->bfs_order : h->cluster_order; }
 
-static int ensure_device_order(gmg_handle h, const std::vector<int>& ord, int** d_ord, int** d_inv) {
-    if (*d_ord) return GMG_OK;
+static int ensure_device_order(gmg_handle h, const std::vector<int>& ord, DevBuf<int>& d_ord, DevBuf<int>& d_inv) {
+    if (d_ord) return GMG_OK;
     const int n = (int)ord.size();
     std::vector<int> inv(n);
     parallel_ranges(n, std::min(h->cfg.host_threads, 32), [&](int lo, int hi, int) { for (int r = lo; r < hi; ++r) inv[ord[r]] = r; });
@@ -157,15 +142,15 @@ int choose_base_order(gmg_handle h, const DevCsr& dA, int n) {
     h->timing["base_order_score_cluster"] = h->timing["base_order_score_bfs"] = h->timing["base_order_choice"] = 0.0;
     if ((int)h->bfs_order.size() != n || (int)h->cluster_order.size() != n) { h->base_order_choice = (int)h->bfs_order.size() == n ? 1 : 0; return GMG_OK; }
     int rc;
-    if ((rc = ensure_device_order(h, h->cluster_order, &h->d_cluster_order, &h->d_cluster_inv)) || (rc = ensure_device_order(h, h->bfs_order, &h->d_bfs_order, &h->d_bfs_inv))) return rc;
-    DevTmp<unsigned long long> acc;
-    if ((rc = acc.alloc(h, 4))) return rc;
-    HIPCHK(hipMemsetAsync(acc.p, 0, sizeof(unsigned long long) * 4, h->stream));
+    if ((rc = ensure_device_order(h, h->cluster_order, h->d_cluster_order, h->d_cluster_inv)) || (rc = ensure_device_order(h, h->bfs_order, h->d_bfs_order, h->d_bfs_inv))) return rc;
+    DevBuf<unsigned long long> acc;
+    if ((rc = dev_alloc(h, acc, 4))) return rc;
+    HIPCHK(hipMemsetAsync(acc, 0, sizeof(unsigned long long) * 4, h->stream));
     const int n_win = 4096;
-    hipLaunchKernelGGL(gmgs::order_gather_score, dim3(n_win / 4), dim3(256), 0, h->stream, dA.ptr, dA.idx, h->d_cluster_order, h->d_cluster_inv, n, n_win, acc.p);
-    hipLaunchKernelGGL(gmgs::order_gather_score, dim3(n_win / 4), dim3(256), 0, h->stream, dA.ptr, dA.idx, h->d_bfs_order, h->d_bfs_inv, n, n_win, acc.p + 2);
+    hipLaunchKernelGGL(gmgs::order_gather_score, dim3(n_win / 4), dim3(256), 0, h->stream, dA.ptr, dA.idx, h->d_cluster_order.get(), h->d_cluster_inv.get(), n, n_win, acc.get());
+    hipLaunchKernelGGL(gmgs::order_gather_score, dim3(n_win / 4), dim3(256), 0, h->stream, dA.ptr, dA.idx, h->d_bfs_order.get(), h->d_bfs_inv.get(), n, n_win, acc + 2);
     unsigned long long host[4] = {0, 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(host, acc.p, sizeof host, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(host, acc, sizeof host, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     const double sc = host[1] ? (double)host[0] / (double)host[1] : 0.0, sb = host[3] ? (double)host[2] / (double)host[3] : 0.0;
     h->timing["base_order_score_cluster"] = sc; h->timing["base_order_score_bfs"] = sb;
@@ -180,17 +165,17 @@ int choose_base_order(gmg_handle h, const DevCsr& dA, int n) {
 int device_permute_pattern(gmg_handle h, const DevCsr& dA, int n, int64_t nnz) {
     int rc;
     const bool bfs = h->base_order_choice == 1;
-    int** d_ord = bfs ? &h->d_bfs_order : &h->d_cluster_order;
-    int** d_inv = bfs ? &h->d_bfs_inv : &h->d_cluster_inv;
+    DevBuf<int>& d_ord = bfs ? h->d_bfs_order : h->d_cluster_order;
+    DevBuf<int>& d_inv = bfs ? h->d_bfs_inv : h->d_cluster_inv;
     if ((rc = ensure_device_order(h, base_order(h), d_ord, d_inv))) return rc;
-    DevTmp<int> len, pptr, pidx;
-    if ((rc = len.alloc(h, n)) || (rc = pptr.alloc(h, (size_t)n + 1)) || (rc = pidx.alloc(h, (size_t)nnz))) return rc;
-    hipLaunchKernelGGL(gmgs::perm_row_lengths, dim3((n + 255) / 256), dim3(256), 0, h->stream, dA.ptr, *d_ord, n, len.p);
-    if ((rc = device_scan<int, int>(h, len.p, n, pptr.p, nullptr))) return rc;
-    hipLaunchKernelGGL(gmgs::perm_fill, dim3((n + 255) / 256), dim3(256), 0, h->stream, dA.ptr, dA.idx, *d_ord, *d_inv, pptr.p, n, pidx.p);
+    DevBuf<int> len, pptr, pidx;
+    if ((rc = dev_alloc(h, len, n)) || (rc = dev_alloc(h, pptr, (size_t)n + 1)) || (rc = dev_alloc(h, pidx, (size_t)nnz))) return rc;
+    hipLaunchKernelGGL(gmgs::perm_row_lengths, dim3((n + 255) / 256), dim3(256), 0, h->stream, dA.ptr.get(), d_ord.get(), n, len.get());
+    if ((rc = device_scan<int, int>(h, len, n, pptr, nullptr))) return rc;
+    hipLaunchKernelGGL(gmgs::perm_fill, dim3((n + 255) / 256), dim3(256), 0, h->stream, dA.ptr.get(), dA.idx.get(), d_ord.get(), d_inv.get(), pptr.get(), n, pidx.get());
     h->reo_ptr.resize((size_t)n + 1);
     h->reo_idx.resize((size_t)nnz);
-    if ((rc = d2h(h, h->reo_ptr.data(), pptr.p, sizeof(int) * ((size_t)n + 1))) || (rc = d2h(h, h->reo_idx.data(), pidx.p, sizeof(int) * (size_t)nnz))) return rc;
+    if ((rc = d2h(h, h->reo_ptr.data(), pptr, sizeof(int) * ((size_t)n + 1))) || (rc = d2h(h, h->reo_idx.data(), pidx, sizeof(int) * (size_t)nnz))) return rc;
     return GMG_OK;
 }
 
@@ -251,17 +236,16 @@ int device_rap(gmg_handle h, const DevCsr& dA, const DevCsr& dU, const DevEll3& 
         std::fprintf(stderr, "[gmg setup] rap nc=%d %-10s %.2f ms\n", nc, what, ms_since(tph));
         tph = clk::now();
     };
-    free_csr(dC);
+    dC = {};
     dC.n_outer = nc;
-    DevTmp<int> cnt;
+    DevBuf<int> cnt;
     int rc;
-    if ((rc = cnt.alloc(h, nc))) return rc;
-    HIPCHK(dev_malloc((void**)&dC.ptr, sizeof(int) * ((size_t)nc + 1)));
+    if ((rc = dev_alloc(h, cnt, nc)) || (rc = dev_alloc(h, dC.ptr, (size_t)nc + 1))) return rc;
     hipLaunchKernelGGL(gmgs::rap_rows<0>, dim3(nc), dim3(64), 0, h->stream, dA.ptr, dA.idx, dA.val, dU.ptr, dU.idx, dU.val, e3.cnt, e3.col, e3.val, nc,
-                       (const int*)nullptr, cnt.p, (int*)nullptr, (double*)nullptr, d_err);
+                       (const int*)nullptr, cnt.get(), (int*)nullptr, (double*)nullptr, d_err);
     phase("count");
     int nnz = 0, herr = 0;
-    if ((rc = device_scan<int, int>(h, cnt.p, nc, dC.ptr, &nnz))) return rc;
+    if ((rc = device_scan<int, int>(h, cnt, nc, dC.ptr, &nnz))) return rc;
     HIPCHK(hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     C.n_outer = nc; C.n_inner = nc;
     if (pattern || values) {
@@ -270,10 +254,9 @@ int device_rap(gmg_handle h, const DevCsr& dA, const DevCsr& dU, const DevEll3& 
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     phase("scan+ptr");
-    if (herr) { free_csr(dC); return 1; }       // a coarse row overflows the device hash set (or a U row has > 3 entries): host fallback
+    if (herr) { dC = {}; return 1; }       // a coarse row overflows the device hash set (or a U row has > 3 entries): host fallback
     *nnz_out = nnz;
-    HIPCHK(dev_malloc((void**)&dC.idx, sizeof(int) * std::max(nnz, 1)));
-    HIPCHK(dev_malloc((void**)&dC.val, sizeof(double) * std::max(nnz, 1)));
+    if ((rc = dev_alloc(h, dC.idx, (size_t)nnz)) || (rc = dev_alloc(h, dC.val, (size_t)nnz))) return rc;
     hipLaunchKernelGGL(gmgs::rap_rows<1>, dim3(nc), dim3(64), 0, h->stream, dA.ptr, dA.idx, dA.val, dU.ptr, dU.idx, dU.val, e3.cnt, e3.col, e3.val, nc,
                        (const int*)dC.ptr, (int*)nullptr, dC.idx, dC.val, d_err);
     phase("numeric");
@@ -314,97 +297,74 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
         std::fprintf(stderr, "[gmg setup] level %d %-10s %.2f ms\n", k, what, ms_since(tph));
         tph = clk::now();
     };
-    struct Ref {
-        int*& p;
-        int alloc(gmg_handle h, size_t n) {
-            if (p) { (void)dev_free(p); p = nullptr; }
-            HIPCHK(dev_malloc((void**)&p, std::max<size_t>(n, 1) * sizeof(int)));
-            return GMG_OK;
-        }
-    };
-    Ref d_old2new{l.d_old2new}, d_blk_of_row{l.d_blk_of_row};       // owned by the level (refresh_system_values reuses them)
+    DevBuf<int> &d_old2new = l.d_old2new, &d_blk_of_row = l.d_blk_of_row;       // owned by the level (refresh_system_values reuses them)
     if (!l.dA.ptr) {
         if ((rc = ensure_host_A(h, k, true)) || (rc = upload_csr(h, l.dA, l.A))) return rc;
     }
     const DevCsr& dA = l.dA;
-    if ((rc = upload(h, &d_old2new.p, l.ord.old2new))) return rc;
+    if ((rc = upload(h, d_old2new, l.ord.old2new))) return rc;
     phase("old2new");
-    gmgs::RowFilter f{rows_k, d_old2new.p, nullptr, nullptr, 0, 1};
+    gmgs::RowFilter f{rows_k, d_old2new, nullptr, nullptr, 0, 1};
     const int lanes_auto = l.n < kQuadLevelRows ? 4 : 1;
     const int lpr = (l.ord.blocked && k > 0) ? (h->cfg.block_lanes ? h->cfg.block_lanes : lanes_auto) : 1;
-    HIPCHK(dev_malloc((void**)&l.diag, sizeof(double) * l.n_pad));
+    if ((rc = dev_alloc(h, l.diag, l.n_pad))) return rc;
     const bool maps = h->part_world <= 1;      // (a partitioned handle releases dA: nothing to refresh from)
     if ((rc = device_build_sell(h, l.Aoff, dA.ptr, dA.ptr + 1, dA.idx, dA.val, f, nullptr, l.n_pad, lpr, nullptr, l.diag, d_err, false, maps ? &l.src_A : nullptr,
                                 maps ? &l.src_diag : nullptr))) return rc;
     l.Aoff.nnz_real = l.nnz - l.n;
     phase("A");
     if (l.ord.blocked) {
-        if ((rc = d_blk_of_row.alloc(h, l.n_pad)) || (rc = upload(h, &l.d_blk_begin, l.ord.blk_begin)) ||
-            (rc = upload(h, &l.d_blk_ncolors, l.ord.blk_ncolors)) || (rc = upload(h, &l.d_row_color, l.ord.row_color))) return rc;
-        hipLaunchKernelGGL(gmgs::block_of_rows, dim3(std::max(1, l.ord.n_blocks())), dim3(64), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), d_blk_of_row.p);
-        gmgs::RowFilter fin{rows_k, d_old2new.p, d_blk_of_row.p, l.d_blk_begin, 1, 1};
-        gmgs::RowFilter fout{rows_k, d_old2new.p, d_blk_of_row.p, l.d_blk_begin, 2, 1};
+        if ((rc = dev_alloc(h, d_blk_of_row, l.n_pad)) || (rc = upload(h, l.d_blk_begin, l.ord.blk_begin)) ||
+            (rc = upload(h, l.d_blk_ncolors, l.ord.blk_ncolors)) || (rc = upload(h, l.d_row_color, l.ord.row_color))) return rc;
+        hipLaunchKernelGGL(gmgs::block_of_rows, dim3(std::max(1, l.ord.n_blocks())), dim3(64), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), d_blk_of_row);
+        gmgs::RowFilter fin{rows_k, d_old2new, d_blk_of_row, l.d_blk_begin, 1, 1};
+        gmgs::RowFilter fout{rows_k, d_old2new, d_blk_of_row, l.d_blk_begin, 2, 1};
         if (wants_block_ep(h, lpr)) {
             // unpadded block sweep (gs_block_ep): "explicit" and "lower" parts as block-ordered CSRs.  Row pointers first:
             // the largest block's chunks size the sweep's LDS buffers
-            gmgs::RowFilter fe{rows_k, d_old2new.p, d_blk_of_row.p, l.d_blk_begin, 3, 1};
-            gmgs::RowFilter fl{rows_k, d_old2new.p, d_blk_of_row.p, l.d_blk_begin, 4, 1};
-            DevTmp<int> len, d_max;
+            gmgs::RowFilter fe{rows_k, d_old2new, d_blk_of_row, l.d_blk_begin, 3, 1};
+            gmgs::RowFilter fl{rows_k, d_old2new, d_blk_of_row, l.d_blk_begin, 4, 1};
+            DevBuf<int> len, d_max;
             int nnz_e = 0, nnz_l = 0, bmax[2] = {0, 0};
-            if ((rc = len.alloc(h, l.n_pad)) || (rc = d_max.alloc(h, 2))) return rc;
-            HIPCHK(dev_malloc((void**)&l.ee_ptr, sizeof(int) * ((size_t)l.n_pad + 1)));
-            HIPCHK(dev_malloc((void**)&l.ep_ptr, sizeof(int) * ((size_t)l.n_pad + 1)));
-            HIPCHK(hipMemsetAsync(d_max.p, 0, 2 * sizeof(int), h->stream));
+            if ((rc = dev_alloc(h, len, l.n_pad)) || (rc = dev_alloc(h, d_max, 2)) || (rc = dev_alloc(h, l.ee_ptr, (size_t)l.n_pad + 1)) || (rc = dev_alloc(h, l.ep_ptr, (size_t)l.n_pad + 1))) return rc;
+            HIPCHK(hipMemsetAsync(d_max.get(), 0, 2 * sizeof(int), h->stream));
             const dim3 gr((l.n_pad + 255) / 256), gb((l.ord.n_blocks() + 255) / 256);
-            hipLaunchKernelGGL(gmgs::row_lengths, gr, dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fe, (const int*)nullptr, l.n_pad, len.p, d_err);
-            if ((rc = device_scan<int, int>(h, len.p, l.n_pad, l.ee_ptr, &nnz_e))) return rc;
-            hipLaunchKernelGGL(gmgs::block_entry_max, gb, dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.ee_ptr, d_max.p);
-            hipLaunchKernelGGL(gmgs::row_lengths, gr, dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fl, (const int*)nullptr, l.n_pad, len.p, d_err);
-            if ((rc = device_scan<int, int>(h, len.p, l.n_pad, l.ep_ptr, &nnz_l))) return rc;
-            hipLaunchKernelGGL(gmgs::block_entry_max, gb, dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.ep_ptr, d_max.p + 1);
-            HIPCHK(hipMemcpyAsync(bmax, d_max.p, 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            hipLaunchKernelGGL(gmgs::row_lengths, gr, dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fe, (const int*)nullptr, l.n_pad, len.get(), d_err);
+            if ((rc = device_scan<int, int>(h, len.get(), l.n_pad, l.ee_ptr, &nnz_e))) return rc;
+            hipLaunchKernelGGL(gmgs::block_entry_max, gb, dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.ee_ptr, d_max.get());
+            hipLaunchKernelGGL(gmgs::row_lengths, gr, dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fl, (const int*)nullptr, l.n_pad, len.get(), d_err);
+            if ((rc = device_scan<int, int>(h, len.get(), l.n_pad, l.ep_ptr, &nnz_l))) return rc;
+            hipLaunchKernelGGL(gmgs::block_entry_max, gb, dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.ep_ptr, d_max.get() + 1);
+            HIPCHK(hipMemcpyAsync(bmax, d_max.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             if (bmax[0] <= kEpMaxBlockEntries && bmax[1] <= kEpMaxBlockLower) {
                 l.use_ep = true;
                 l.ee_nnz = nnz_e; l.ep_nnz = nnz_l;
                 l.ep_cap_e = (bmax[0] + 63) / 64 * 64; l.ep_cap_l = std::max(bmax[1], 1);
-                HIPCHK(dev_malloc((void**)&l.ee_col, sizeof(int) * (size_t)std::max(nnz_e, 1)));
-                HIPCHK(dev_malloc((void**)&l.ee_val, sizeof(double) * (size_t)std::max(nnz_e, 1)));
-                HIPCHK(dev_malloc((void**)&l.ep_col, sizeof(unsigned short) * (size_t)std::max(nnz_l, 1)));
-                HIPCHK(dev_malloc((void**)&l.ep_val, sizeof(double) * (size_t)std::max(nnz_l, 1)));
-                if (maps) {
-                    for (int** q : {&l.src_ee, &l.src_ep}) { if (*q) (void)dev_free(*q); *q = nullptr; }
-                    HIPCHK(dev_malloc((void**)&l.src_ee, sizeof(int) * (size_t)std::max(nnz_e, 1)));
-                    HIPCHK(dev_malloc((void**)&l.src_ep, sizeof(int) * (size_t)std::max(nnz_l, 1)));
-                }
+                if ((rc = dev_alloc(h, l.ee_col, (size_t)nnz_e)) || (rc = dev_alloc(h, l.ee_val, (size_t)nnz_e)) || (rc = dev_alloc(h, l.ep_col, (size_t)nnz_l)) || (rc = dev_alloc(h, l.ep_val, (size_t)nnz_l))) return rc;
+                if (maps && ((rc = dev_alloc(h, l.src_ee, (size_t)nnz_e)) || (rc = dev_alloc(h, l.src_ep, (size_t)nnz_l)))) return rc;
                 launch_csr_fill_plain(h, l, dA, fe, fl, d_err);
-            } else {
-                (void)dev_free(l.ee_ptr); l.ee_ptr = nullptr;
-                (void)dev_free(l.ep_ptr); l.ep_ptr = nullptr;
-            }
+            } else { l.ee_ptr = {}; l.ep_ptr = {}; }
         }
         if (!l.use_ep && wants_block_csr(h, lpr)) {
             // off-block operator as a block-ordered CSR; its row pointers first: they tell whether the largest block's
             // chunk fits the sweep's LDS budget
-            DevTmp<int> len, d_max;
+            DevBuf<int> len, d_max;
             int nnz = 0, bmax = 0;
-            if ((rc = len.alloc(h, l.n_pad)) || (rc = d_max.alloc(h, 1))) return rc;
-            HIPCHK(dev_malloc((void**)&l.bc_ptr, sizeof(int) * ((size_t)l.n_pad + 1)));
-            HIPCHK(hipMemsetAsync(d_max.p, 0, sizeof(int), h->stream));
-            hipLaunchKernelGGL(gmgs::row_lengths, dim3((l.n_pad + 255) / 256), dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fout, (const int*)nullptr, l.n_pad, len.p, d_err);
-            if ((rc = device_scan<int, int>(h, len.p, l.n_pad, l.bc_ptr, &nnz))) return rc;
-            hipLaunchKernelGGL(gmgs::block_entry_max, dim3((l.ord.n_blocks() + 255) / 256), dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.bc_ptr, d_max.p);
-            HIPCHK(hipMemcpyAsync(&bmax, d_max.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            if ((rc = dev_alloc(h, len, l.n_pad)) || (rc = dev_alloc(h, d_max, 1)) || (rc = dev_alloc(h, l.bc_ptr, (size_t)l.n_pad + 1))) return rc;
+            HIPCHK(hipMemsetAsync(d_max.get(), 0, sizeof(int), h->stream));
+            hipLaunchKernelGGL(gmgs::row_lengths, dim3((l.n_pad + 255) / 256), dim3(256), 0, h->stream, dA.ptr, dA.ptr + 1, dA.idx, fout, (const int*)nullptr, l.n_pad, len.get(), d_err);
+            if ((rc = device_scan<int, int>(h, len.get(), l.n_pad, l.bc_ptr, &nnz))) return rc;
+            hipLaunchKernelGGL(gmgs::block_entry_max, dim3((l.ord.n_blocks() + 255) / 256), dim3(256), 0, h->stream, l.d_blk_begin, l.ord.n_blocks(), l.bc_ptr, d_max.get());
+            HIPCHK(hipMemcpyAsync(&bmax, d_max.get(), sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
             if (bmax <= kBcsrMaxBlockEntries) {
                 l.use_bcsr = true;
                 l.bc_cap = (bmax + 63) / 64 * 64;
                 l.bc_nnz = nnz;
-                HIPCHK(dev_malloc((void**)&l.bc_mid, sizeof(int) * (size_t)l.n_pad));
-                HIPCHK(dev_malloc((void**)&l.bc_col, sizeof(int) * (size_t)std::max(nnz, 1)));
-                HIPCHK(dev_malloc((void**)&l.bc_val, sizeof(double) * (size_t)std::max(nnz, 1)));
-                launch_csr_fill(h, l, dA, fout, d_blk_of_row.p, d_err);
-            } else { (void)dev_free(l.bc_ptr); l.bc_ptr = nullptr; }
+                if ((rc = dev_alloc(h, l.bc_mid, (size_t)l.n_pad)) || (rc = dev_alloc(h, l.bc_col, (size_t)nnz)) || (rc = dev_alloc(h, l.bc_val, (size_t)nnz))) return rc;
+                launch_csr_fill(h, l, dA, fout, d_blk_of_row, d_err);
+            } else l.bc_ptr = {};
         }
         if (!l.use_ep) {
             // (the unpadded sweep reads its two block-ordered CSR operators only: no padded SELL copies of the split operator)
@@ -421,8 +381,8 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
     const int* rows_c = own_rows_next ? own_rows_next : c.d_new2old;
     const DevCsr& dU = h->dU[k];
     const DevEll3& e3 = h->dE3[k];
-    DevTmp<int> d_old2new_c, d_order, d_pbeg, d_pend;
-    if ((rc = upload(h, &d_old2new_c.p, c.ord.old2new))) return rc;
+    DevBuf<int> d_old2new_c, d_order, d_pbeg, d_pend;
+    if ((rc = upload(h, d_old2new_c, c.ord.old2new))) return rc;
     // restriction: rows = coarse points (columns of the CSC U), sorted by length inside windows like the host planner
     {
         const Compressed& U = h->U[k];
@@ -430,8 +390,8 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
         if (sigma > 0 && sigma <= gmgs::kWindowSortMax) {
             int pow2 = 1;
             while (pow2 < sigma) pow2 <<= 1;
-            if ((rc = d_order.alloc(h, np))) return rc;
-            hipLaunchKernelGGL(gmgs::window_order_by_length, dim3((np + sigma - 1) / sigma), dim3(256), 0, h->stream, dU.ptr, rows_c, np, sigma, pow2, d_order.p);
+            if ((rc = dev_alloc(h, d_order, np))) return rc;
+            hipLaunchKernelGGL(gmgs::window_order_by_length, dim3((np + sigma - 1) / sigma), dim3(256), 0, h->stream, dU.ptr, rows_c, np, sigma, pow2, d_order.get());
         } else if (sigma > 0) {
             std::vector<int> order(np);
             auto len_of = [&](int r) { int old = c.ord.new2old[r]; return old >= 0 ? U.ptr[old + 1] - U.ptr[old] : 0; };
@@ -441,24 +401,24 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
                 std::iota(order.begin() + w, order.begin() + we, w);
                 std::stable_sort(order.begin() + w, order.begin() + we, [&](int a, int b) { return len_of(a) > len_of(b); });
             }
-            if ((rc = upload(h, &d_order.p, order))) return rc;
+            if ((rc = upload(h, d_order, order))) return rc;
             HIPCHK(hipStreamSynchronize(h->stream));      // `order` (pageable) dies at scope end
         }
         phase("R order");
-        gmgs::RowFilter fr{rows_c, d_old2new.p, nullptr, nullptr, 0, 0};
+        gmgs::RowFilter fr{rows_c, d_old2new, nullptr, nullptr, 0, 0};
         const int lpr_r = h->cfg.block_lanes == 1 ? 1 : 4;
-        if ((rc = device_build_sell(h, l.R, dU.ptr, dU.ptr + 1, dU.idx, dU.val, fr, sigma > 0 ? d_order.p : nullptr, np, lpr_r, nullptr, nullptr, d_err))) return rc;
+        if ((rc = device_build_sell(h, l.R, dU.ptr, dU.ptr + 1, dU.idx, dU.val, fr, sigma > 0 ? d_order.get() : nullptr, np, lpr_r, nullptr, nullptr, d_err))) return rc;
         l.R.nnz_real = U.nnz();
-        if (sigma > 0) { l.R.row_of = d_order.p; d_order.p = nullptr; }     // the order array becomes the output-row map
+        if (sigma > 0) l.R.row_of = std::move(d_order);     // the order array becomes the output-row map
         phase("R");
     }
     // prolongation: rows = fine points; U is stored by coarse column, so it was regrouped by fine row (<= 3 per row)
     {
         const int nf = l.n;
-        if ((rc = d_pbeg.alloc(h, nf)) || (rc = d_pend.alloc(h, nf))) return rc;
-        hipLaunchKernelGGL(gmgs::ell3_ptr, dim3((nf + 255) / 256), dim3(256), 0, h->stream, e3.cnt, nf, d_pbeg.p, d_pend.p);
-        gmgs::RowFilter fp{rows_k, d_old2new_c.p, nullptr, nullptr, 0, 0};
-        if ((rc = device_build_sell(h, l.P, d_pbeg.p, d_pend.p, e3.col, e3.val, fp, nullptr, l.n_pad, 1, nullptr, nullptr, d_err))) return rc;
+        if ((rc = dev_alloc(h, d_pbeg, nf)) || (rc = dev_alloc(h, d_pend, nf))) return rc;
+        hipLaunchKernelGGL(gmgs::ell3_ptr, dim3((nf + 255) / 256), dim3(256), 0, h->stream, e3.cnt, nf, d_pbeg.get(), d_pend.get());
+        gmgs::RowFilter fp{rows_k, d_old2new_c, nullptr, nullptr, 0, 0};
+        if ((rc = device_build_sell(h, l.P, d_pbeg.get(), d_pend.get(), e3.col, e3.val, fp, nullptr, l.n_pad, 1, nullptr, nullptr, d_err))) return rc;
         l.P.nnz_real = h->U[k].nnz();
     }
     // ---- 16-bit column codes of level 0's operator and transfers for the fine-level kernels (kernels.hip.hpp; gmg_config::fine_col16 = 0: 32-bit indices only): 2 of
@@ -468,24 +428,23 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
     DevSell* c16_ops[3] = {&l.Aoff, &l.R, &l.P};
     const char* c16_keys[3] = {"col16_l0", "col16_R_l0", "col16_P_l0"};
     int c16_failed[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // per operator: uncovered slices, 1 + index of the last of them; [6 + i]: slices of another width than the mean
-    DevTmp<int> d_c16;
+    DevBuf<int> d_c16;
     const bool c16 = k == 0 && h->cfg.fine_col16 != 0;      // (a blocked level 0 too: its residual-check and transfer kernels are the colour-major level's)
     const int c16_test_fail = h->dbg_col16_uncovered;         // gmg_debug_set (gravomg_hip_internal.h): N > 0 every N-th slice "uncovered", N < 0 the first -N
     int c16_wexp[3] = {-1, -1, -1};
     auto c16_launch = [&](int i, int nw) -> int {
         DevSell& op = *c16_ops[i];
-        if (op.win_base) { (void)dev_free(op.win_base); op.win_base = nullptr; }
-        if (!op.col16) HIPCHK(dev_malloc((void**)&op.col16, sizeof(unsigned) * (size_t)op.stored));
-        HIPCHK(dev_malloc((void**)&op.win_base, sizeof(int) * (size_t)op.n_slices * nw));
-        HIPCHK(hipMemsetAsync(d_c16.p + 2 * i, 0, 2 * sizeof(int), h->stream));
-        HIPCHK(hipMemsetAsync(d_c16.p + 6 + i, 0, sizeof(int), h->stream));
+        int r2;
+        if ((!op.col16 && (r2 = dev_alloc(h, op.col16, (size_t)op.stored))) || (r2 = dev_alloc(h, op.win_base, (size_t)op.n_slices * nw))) return r2;
+        HIPCHK(hipMemsetAsync(d_c16.get() + 2 * i, 0, 2 * sizeof(int), h->stream));
+        HIPCHK(hipMemsetAsync(d_c16.get() + 6 + i, 0, sizeof(int), h->stream));
         const int64_t per_slice = op.stored / ((int64_t)op.n_slices * 64);
         const int w_exp = (per_slice >= 1 && per_slice <= 63 && per_slice * op.n_slices * 64 == op.stored && h->cfg.uniform_slices) ? (int)per_slice : -1;
         c16_wexp[i] = w_exp;
         const int* a_ptr = i == 0 ? dA.ptr : (const int*)nullptr;
         const int* n2o = i == 0 ? rows_k : (const int*)nullptr;
-        if (nw == 8) hipLaunchKernelGGL(gmgs::compress_cols<8>, dim3((op.n_slices + 3) / 4), dim3(256), 0, h->stream, op.slice_ptr, op.col, a_ptr, n2o, op.val, op.n_slices, c16_test_fail, op.col16, op.win_base, d_c16.p + 2 * i, w_exp, d_c16.p + 6 + i);
-        else hipLaunchKernelGGL(gmgs::compress_cols<32>, dim3((op.n_slices + 3) / 4), dim3(256), 0, h->stream, op.slice_ptr, op.col, a_ptr, n2o, op.val, op.n_slices, c16_test_fail, op.col16, op.win_base, d_c16.p + 2 * i, w_exp, d_c16.p + 6 + i);
+        if (nw == 8) hipLaunchKernelGGL(gmgs::compress_cols<8>, dim3((op.n_slices + 3) / 4), dim3(256), 0, h->stream, op.slice_ptr, op.col, a_ptr, n2o, op.val, op.n_slices, c16_test_fail, op.col16, op.win_base, d_c16.get() + 2 * i, w_exp, d_c16.get() + 6 + i);
+        else hipLaunchKernelGGL(gmgs::compress_cols<32>, dim3((op.n_slices + 3) / 4), dim3(256), 0, h->stream, op.slice_ptr, op.col, a_ptr, n2o, op.val, op.n_slices, c16_test_fail, op.col16, op.win_base, d_c16.get() + 2 * i, w_exp, d_c16.get() + 6 + i);
         op.c16_dbits = nw == 8 ? 13 : 11;
         return GMG_OK;
     };
@@ -494,13 +453,13 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
     auto c16_mode_of = [&](int i) { const DevSell& op = *c16_ops[i]; return c16_failed[2 * i + 1] <= op.n_slices / 16 ? 1 : (c16_failed[2 * i] <= op.n_slices / 8 ? 2 : 0); };
     if (k == 0) for (const char* key : c16_keys) h->timing[key] = 0.0;
     if (c16) {
-        if ((rc = d_c16.alloc(h, 9))) return rc;
+        if ((rc = dev_alloc(h, d_c16, 9))) return rc;
         for (int i = 0; i < 3; ++i) {
             DevSell& op = *c16_ops[i];
             if (op.stored <= 0 || op.n_slices <= 0 || op.n_slices >= (1 << 24) || (i == 0 && op.lpr != 1)) continue;
             if ((rc = c16_launch(i, 8))) return rc;
         }
-        HIPCHK(hipMemcpyAsync(c16_failed, d_c16.p, 9 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(c16_failed, d_c16.get(), 9 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));      // uploads from the orderings' (pageable) arrays are done
     if (c16) {
@@ -508,7 +467,7 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
         for (int i = 0; i < 3; ++i)
             if (c16_ops[i]->col16 && c16_mode_of(i) == 0) { if ((rc = c16_launch(i, 32))) return rc; again = true; }
         if (again) {
-            HIPCHK(hipMemcpyAsync(c16_failed, d_c16.p, 9 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipMemcpyAsync(c16_failed, d_c16.get(), 9 * sizeof(int), hipMemcpyDeviceToHost, h->stream));
             HIPCHK(hipStreamSynchronize(h->stream));
         }
         for (int i = 0; i < 3; ++i) {
@@ -519,7 +478,7 @@ int device_layout_level(gmg_handle h, int k, int* d_err, const int* own_rows = n
             op.c16_from = c16_failed[2 * i + 1];
             op.uniform_w = (c16_wexp[i] > 0 && c16_failed[6 + i] == 0) ? c16_wexp[i] : 0;
             h->timing[std::string(c16_keys[i]) + "_uniform_width"] = op.uniform_w;
-            if (op.c16_mode == 0) { (void)dev_free(op.col16); (void)dev_free(op.win_base); op.col16 = nullptr; op.win_base = nullptr; op.c16_dbits = 13; op.c16_from = 0; op.uniform_w = 0; }
+            if (op.c16_mode == 0) { op.col16 = {}; op.win_base = {}; op.c16_dbits = 13; op.c16_from = 0; op.uniform_w = 0; }
             else h->timing[c16_keys[i]] = 1.0;
             h->timing[std::string(c16_keys[i]) + "_windows"] = op.col16 ? (op.c16_dbits == 13 ? 8 : 32) : 0;
             h->timing[std::string(c16_keys[i]) + "_mode"] = op.c16_mode;

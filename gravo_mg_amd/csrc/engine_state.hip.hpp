@@ -74,19 +74,24 @@ struct PoolScope {
 static inline hipError_t dev_malloc(void** p, size_t bytes) { return tl_pool ? tl_pool->alloc(p, bytes) : hipMalloc(p, bytes); }
 static inline hipError_t dev_free(void* p) { if (!p) return hipSuccess; if (tl_pool) { tl_pool->release(p); return hipSuccess; } return sync_hipFree(p); }
 
+// Every array taken with dev_malloc lives in a DevBuf (dev_buf.hpp), which gives it back here -- to the pool of the handle whose PoolScope is
+// active on the thread: owners are destroyed, reset and assigned to inside the C-ABI calls of their handle only (gmg_destroy included).
+#include "dev_buf.hpp"
+inline void dev_buf_release(void* p) { (void)dev_free(p); }
+
 namespace {
 
 struct DevSell {
     int n_slices = 0;
     int lpr = 1;                  // lanes per row of the SELL layout (1 or 4)
     int64_t stored = 0, nnz_real = 0;
-    int64_t* slice_ptr = nullptr;
-    int* col = nullptr;
-    double* val = nullptr;
-    float* val32 = nullptr;       // fp32 copy of val (mixed-precision inner cycle); shares slice_ptr / col / row_of
-    int* row_of = nullptr;
-    unsigned* col16 = nullptr;         // level 0: 16-bit column codes, two to a word, indexed like col (the first half of every slice's region is used)
-    int* win_base = nullptr;           //          + the window bases of every slice, first one -1 = slice on 32-bit indices (gmgs::compress_cols); null = the kernels read col
+    DevBuf<int64_t> slice_ptr;
+    DevBuf<int> col;
+    DevBuf<double> val;
+    DevBuf<float> val32;          // fp32 copy of val (mixed-precision inner cycle); shares slice_ptr / col / row_of
+    DevBuf<int> row_of;
+    DevBuf<unsigned> col16;            // level 0: 16-bit column codes, two to a word, indexed like col (the first half of every slice's region is used)
+    DevBuf<int> win_base;              //          + the window bases of every slice, first one -1 = slice on 32-bit indices (gmgs::compress_cols); null = the kernels read col
     int c16_dbits = 13;                //          offset bits of a code: 13 = 8 windows of 8 192 columns per slice, 11 = 32 windows of 2 048
     int c16_mode = 0;                  //          0 none, 1 codes from slice c16_from on (uncovered slices are a short prefix), 2 uncovered slices flagged one by one
     int c16_from = 0;
@@ -99,15 +104,15 @@ struct DevSell {
 // natural-numbering compressed matrix on the device (A_k, U_k by coarse column)
 struct DevCsr {
     int n_outer = 0;
-    int *ptr = nullptr, *idx = nullptr;
-    double* val = nullptr;
+    DevBuf<int> ptr, idx;
+    DevBuf<double> val;
 };
 
 // U_k regrouped by fine row (<= 3 entries per row, sorted by coarse column) for the prolongation layout and the RAP.
 struct DevEll3 {
     int n = 0;
-    int *cnt = nullptr, *col = nullptr;
-    double* val = nullptr;
+    DevBuf<int> cnt, col;
+    DevBuf<double> val;
 };
 
 struct Level {
@@ -118,39 +123,39 @@ struct Level {
     bool hostA_pattern = false, hostA_values = false;
     DevCsr dA;                    // natural numbering, device copy: RAP input, layout source, source of the lazy host copy
     DevSell Aoff;                 // off-diagonal part, device numbering
-    double* diag = nullptr;       // n_pad
+    DevBuf<double> diag;          // n_pad
     double cheby_lambda = 0.0;    // GMG_SMOOTHER_CHEBYSHEV: Gershgorin bound of D^-1 A_k (finish_system -> compute_cheby_bounds); 0 = not computed
     DevSell P, R;                 // U_k (rows: this level) and U_k^T (rows: next level); unused on level L
     // blocked levels (block-hybrid Gauss-Seidel): in-block part (16-bit local columns) + off-block part
     DevSell Ain, Aout;
-    unsigned short* ain_col16 = nullptr;
+    DevBuf<unsigned short> ain_col16;
     // big blocked levels: block-CSR storage instead of the two padded SELL operators (kernels.hip.hpp::gs_block_csrout)
     bool use_bcsr = false;
-    int *bc_ptr = nullptr, *bc_mid = nullptr, *bc_col = nullptr;
-    double* bc_val = nullptr;
-    float* bc_val32 = nullptr;
+    DevBuf<int> bc_ptr, bc_mid, bc_col;
+    DevBuf<double> bc_val;
+    DevBuf<float> bc_val32;
     int bc_cap = 0;               // entries of the largest block, rounded up to 64 (LDS capacity of the sweep)
     int64_t bc_nnz = 0;
     // big blocked levels, default: the unpadded block sweep (kernels.hip.hpp::gs_block_ep) on two block-ordered CSRs --
     // ee_*: "explicit" part (off-block entries + in-block entries with a later column; device columns),
     // ep_*: "lower" part (in-block entries with an earlier column; 16-bit local columns).  No SELL split, no bc_* then.
     bool use_ep = false;
-    int *ee_ptr = nullptr, *ee_col = nullptr, *ep_ptr = nullptr;
-    unsigned short* ep_col = nullptr;
-    double *ee_val = nullptr, *ep_val = nullptr;
-    float *ee_val32 = nullptr, *ep_val32 = nullptr;
+    DevBuf<int> ee_ptr, ee_col, ep_ptr;
+    DevBuf<unsigned short> ep_col;
+    DevBuf<double> ee_val, ep_val;
+    DevBuf<float> ee_val32, ep_val32;
     int64_t ee_nnz = 0, ep_nnz = 0;
     int ep_cap_e = 0, ep_cap_l = 0;      // most explicit / lower entries of one block (explicit: rounded up to 64): LDS capacity of the sweep
-    int *d_blk_begin = nullptr, *d_blk_ncolors = nullptr;
-    unsigned char* d_row_color = nullptr;
+    DevBuf<int> d_blk_begin, d_blk_ncolors;
+    DevBuf<unsigned char> d_row_color;
     // where every stored slot of the operator layouts came from in dA.val (-1: padding), made with the layouts: a system with the live
     // sparsity pattern refreshes the values by plain gathers (engine_setup.hip.hpp::device_refill_level); not made for a partitioned set-up
-    int *src_A = nullptr, *src_diag = nullptr, *src_ee = nullptr, *src_ep = nullptr;
-    int* d_new2old = nullptr;
-    int* d_old2new = nullptr;         // kept after the layout (with d_blk_of_row) so that a system with the same pattern can
-    int* d_blk_of_row = nullptr;      // refill the value arrays in place (refresh_system_values)
-    double *x = nullptr, *b = nullptr, *r = nullptr, *tmp = nullptr;   // n_pad * dcap
-    float *diag32 = nullptr, *x32 = nullptr, *b32 = nullptr, *r32 = nullptr, *tmp32 = nullptr;   // mixed precision
+    DevBuf<int> src_A, src_diag, src_ee, src_ep;
+    DevBuf<int> d_new2old;
+    DevBuf<int> d_old2new;            // kept after the layout (with d_blk_of_row) so that a system with the same pattern can
+    DevBuf<int> d_blk_of_row;         // refill the value arrays in place (refresh_system_values)
+    DevBuf<double> x, b, r, tmp;      // n_pad * dcap (x, b, r of level 0: the caller's while gmg_dist_bind has them bound, DevBuf::borrow)
+    DevBuf<float> diag32, x32, b32, r32, tmp32;      // mixed precision
 };
 
 }  // namespace
@@ -207,7 +212,7 @@ struct gmg_solver_s {
     // patches of the blocked levels k >= 1, grown over the coarse point graph of U_{k-1} (hierarchy data, host only)
     std::vector<PatchSet> patches;
     std::vector<int> cluster_order;       // locality-preserving order of the level-0 points derived from U (new -> old)
-    int *d_cluster_order = nullptr, *d_cluster_inv = nullptr;      // device copies (order, and old -> new position)
+    DevBuf<int> d_cluster_order, d_cluster_inv;      // device copies (order, and old -> new position)
     std::vector<int> bfs_order;           // ... and the breadth-first order over the point graph, when the caller / the hierarchy object supplied one (gmg_set_fine_order)
     // The pattern the next systems are expected to have (gmg_set_fine_graph / gmg_use_hierarchy).  gmg_finalize_hierarchy then builds everything
     // STRUCTURAL for it -- orderings, colourings, layouts, symbolic Galerkin products, symbolic LDL^T: a whole set-up on placeholder values --
@@ -215,7 +220,7 @@ struct gmg_solver_s {
     // pattern digest equals the prepared one only moves values (refresh_system_values), like any later system with the live pattern.
     std::shared_ptr<const FineGraph> fine_graph;
     bool mass_dirty = false;              // h->mass changed while no ordering existed to permute it with: uploaded by the next set-up / refresh
-    int *d_bfs_order = nullptr, *d_bfs_inv = nullptr;
+    DevBuf<int> d_bfs_order, d_bfs_inv;
     int base_order_choice = 0;            // what the last reordered set-up used: 0 cluster order, 1 breadth-first order
     RawVec<int> reo_ptr, reo_idx;         // LHS pattern permuted into cluster order (staging for the level-0 colouring)
     bool patches_ready = false;
@@ -225,27 +230,27 @@ struct gmg_solver_s {
     SupernodalLDLT coarse;
     LiveSystem live = LiveSystem::none;
     int dcap = 0;
-    double *d_mass = nullptr, *d_minv = nullptr;
-    double* d_stage = nullptr; size_t stage_cap = 0;
+    DevBuf<double> d_mass, d_minv;
+    DevBuf<double> d_stage; size_t stage_cap = 0;
     double* h_stage[2] = {nullptr, nullptr}; size_t h_stage_cap = 0;      // pinned host staging (double-buffered) for b / x
     void* bounce[2] = {nullptr, nullptr};                                  // pinned bounce buffers for the set-up's pageable copies
     hipEvent_t bounce_ev[2] = {nullptr, nullptr}; int bounce_flip = 0;
     hipEvent_t h_stage_ev[2] = {nullptr, nullptr}; int h_stage_flip = 0;
     hipEvent_t h_chunk_ev[16] = {};      // per-chunk arrival of a download (to_host): 8 per staging buffer
-    double* d_partials = nullptr; int partial_blocks = 0;
-    double* d_norm = nullptr;
+    DevBuf<double> d_partials; int partial_blocks = 0;
+    DevBuf<double> d_norm;
     // The accelerated solve loop (gmg_config::accelerate = m > 0; engine.hip::solve_common): 2 (m - 1) + 3 level-0 vectors (n_pad x d) from the
     // pool -- the previous iterate, the recurrence residual, the raw step z0, and the ring of m - 1 stored directions (z_j, q_j = A z_j) -- plus the
     // device-side scalars and the partial sums of its kernels.  Allocated by the first accelerated solve (ensure_accel), released with the level
-    // vectors (drop_accel: ensure_vectors, drop_system).
+    // vectors (accel = {}: ensure_vectors, drop_system).
     struct AccelState {
-        double *xk = nullptr, *r = nullptr, *z0 = nullptr;
-        double* zs[gmg::kAccelMaxStored] = {};
-        double* qs[gmg::kAccelMaxStored] = {};
-        double* scal = nullptr;          // alpha[d], guarded[d], beta[3][d], s_j[3][d], guarded steps of the solve: 8 d + 1 doubles
+        DevBuf<double> xk, r, z0;
+        DevBuf<double> zs[gmg::kAccelMaxStored];
+        DevBuf<double> qs[gmg::kAccelMaxStored];
+        DevBuf<double> scal;             // alpha[d], guarded[d], beta[3][d], s_j[3][d], guarded steps of the solve: 8 d + 1 doubles
                                          // (s_j = 0: slot j holds no usable direction for that column -- never stored, or stored by a guarded step:
                                          // its vector entries may be anything and are not looked at, accel_kernels.hip.hpp::AccelRing)
-        double* partials = nullptr;      // kAccelMaxBlocks x kAccelMaxComp
+        DevBuf<double> partials;         // kAccelMaxBlocks x kAccelMaxComp
         int depth = 0, d = 0, n_pad = 0;
     } accel;
     // Head of the next cycle (gmg_config::speculate_head; engine.hip::solve_common): the solve loop's decision is taken by the check's
@@ -253,7 +258,7 @@ struct gmg_solver_s {
     // host has seen the norm, and returns at once when the iteration stopped.  Only the device words live here: what the reduction needs to
     // decide, and whether a head is in the stream, are the loop's locals and reach the launches as arguments (engine_cycle.hip.hpp: CycleWatch,
     // vcycle_resident) -- like everything else one launch of a cycle hands to another (SmoothAsk / SmoothDone): the handle keeps no such state.
-    double* d_watch = nullptr;
+    DevBuf<double> d_watch;
     double* h_pinned = nullptr; size_t pinned_cap = 0;     // coarse rhs / solution staging
     double* h_norm = nullptr;
     // polled completion (stream launches only): a kernel writes its small result into pinned memory and then a sequence
@@ -269,12 +274,12 @@ struct gmg_solver_s {
     double coarse_warm_sink = 0.0;
     int coarse_pending_d = 0;
     bool poll = true;             // GMG_POLL=0: copy + hipStreamSynchronize instead (the waiting thread then sleeps instead of spinning)
-    double* d_ainv = nullptr;                              // coarse_device: dense A_L^-1, level numbering (engine_system.hip.hpp::build_coarse_inverse_device)
+    DevBuf<double> d_ainv;                                 // coarse_device: dense A_L^-1, level numbering (engine_system.hip.hpp::build_coarse_inverse_device)
     int ainv_n = 0, ainv_ld = 0;                           // ... n x n with rows ainv_ld doubles apart (n rounded up to 8: rows at 64-byte boundaries)
     // GMG_COARSE_DEVICE_TRIANGLE instead: the packed lower triangle in the factor's numbering (coarse_triangle.hpp), the permutation factor -> level
     // the product gathers and scatters through, and the product's row / column partials of one column group -- all made at set-up
-    double *d_tri = nullptr, *d_tri_row = nullptr, *d_tri_col = nullptr;
-    int* d_tri_perm = nullptr;
+    DevBuf<double> d_tri, d_tri_row, d_tri_col;
+    DevBuf<int> d_tri_perm;
     int tri_n = -1;                                        // n_L the four buffers are sized for (-1: none)
     bool coarse_triangle = false;                          // coarse_device, applied from d_tri (decided per system)
     int64_t fused_restrictions = 0;                       // restrictions enqueued together with the next level's first pre-sweep (restrict_into; timing key "restrict_sweeps_fused")
@@ -314,7 +319,7 @@ struct gmg_solver_s {
     bool live_from_copy = false;      // the live system was set up from the engine's canonical copy of the caller's arrays (unsorted / duplicate entries): the
                                       // resident A_0 is NOT in the caller's storage order (gmg_set_system_values_device refuses)
     bool dist_all_rows = false;
-    double *own_x0 = nullptr, *own_b0 = nullptr, *own_r0 = nullptr;   // engine-owned buffers parked while external ones are bound
+    DevBuf<double> own_x0, own_b0, own_r0;      // engine-owned buffers parked while external ones are bound
     bool bound = false;
     // orderings of the last system, reusable while the sparsity pattern of the LHS and the hierarchy are unchanged
     bool ord_cache_valid = false;
@@ -437,67 +442,37 @@ static int d2h(gmg_handle h, void* dst, const void* src, size_t bytes) {
     return GMG_OK;
 }
 
-template <class T, class A>
-int upload(gmg_handle h, T** dst, const std::vector<T, A>& src) {
-    if (*dst) { (void)dev_free(*dst); *dst = nullptr; }
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    HIPCHK(dev_malloc((void**)dst, bytes));
-    if (!src.empty()) return h2d(h, *dst, src.data(), src.size() * sizeof(T));
-    return GMG_OK;
-}
-
+// `count` elements (at least one) from the pool into `buf`, whose old block goes back first
 template <class T>
-int upload(gmg_handle h, T** dst, const RawVec<T>& src) {
-    if (*dst) { (void)dev_free(*dst); *dst = nullptr; }
-    size_t bytes = std::max<size_t>(src.size(), 1) * sizeof(T);
-    HIPCHK(dev_malloc((void**)dst, bytes));
-    if (!src.empty()) return h2d(h, *dst, src.data(), src.size() * sizeof(T));
+int dev_alloc(gmg_handle h, DevBuf<T>& buf, size_t count) {
+    buf.reset();
+    T* p = nullptr;
+    HIPCHK(dev_malloc((void**)&p, std::max<size_t>(count, 1) * sizeof(T)));
+    buf.adopt(p);
     return GMG_OK;
 }
 
-void free_sell(DevSell& s) {
-    if (s.slice_ptr) (void)dev_free(s.slice_ptr);
-    if (s.col) (void)dev_free(s.col);
-    if (s.val) (void)dev_free(s.val);
-    if (s.val32) (void)dev_free(s.val32);
-    if (s.row_of) (void)dev_free(s.row_of);
-    if (s.col16) (void)dev_free(s.col16);
-    if (s.win_base) (void)dev_free(s.win_base);
-    s = DevSell();
+template <class T, class Vec>        // Vec: std::vector<T, A> or RawVec<T>
+int upload(gmg_handle h, DevBuf<T>& dst, const Vec& src) {
+    static_assert(std::is_same<decltype(src.data()), const T*>::value, "element types of the buffer and its source");
+    int rc = dev_alloc(h, dst, src.size());
+    if (rc == GMG_OK && !src.empty()) rc = h2d(h, dst, src.data(), src.size() * sizeof(T));
+    return rc;
 }
 
 int upload_sell(gmg_handle h, DevSell& d, const SellHost& s) {
-    free_sell(d);
+    d = {};
     d.n_slices = s.n_slices; d.stored = s.stored(); d.nnz_real = s.nnz_real; d.lpr = s.lpr;
     int rc;
-    if ((rc = upload(h, &d.slice_ptr, s.slice_ptr))) return rc;
-    if ((rc = upload(h, &d.col, s.col))) return rc;
-    if ((rc = upload(h, &d.val, s.val))) return rc;
-    if (!s.row_of.empty() && (rc = upload(h, &d.row_of, s.row_of))) return rc;
+    if ((rc = upload(h, d.slice_ptr, s.slice_ptr))) return rc;
+    if ((rc = upload(h, d.col, s.col))) return rc;
+    if ((rc = upload(h, d.val, s.val))) return rc;
+    if (!s.row_of.empty() && (rc = upload(h, d.row_of, s.row_of))) return rc;
     return GMG_OK;
 }
 
-void free_csr(DevCsr& m) {
-    if (m.ptr) (void)dev_free(m.ptr);
-    if (m.idx) (void)dev_free(m.idx);
-    if (m.val) (void)dev_free(m.val);
-    m = DevCsr();
-}
-
-void free_ell3(DevEll3& e) {
-    if (e.cnt) (void)dev_free(e.cnt);
-    if (e.col) (void)dev_free(e.col);
-    if (e.val) (void)dev_free(e.val);
-    e = DevEll3();
-}
-
 void drop_device_transfers(gmg_handle h) {
-    if (h->d_cluster_order) { (void)dev_free(h->d_cluster_order); h->d_cluster_order = nullptr; }
-    if (h->d_cluster_inv) { (void)dev_free(h->d_cluster_inv); h->d_cluster_inv = nullptr; }
-    if (h->d_bfs_order) { (void)dev_free(h->d_bfs_order); h->d_bfs_order = nullptr; }
-    if (h->d_bfs_inv) { (void)dev_free(h->d_bfs_inv); h->d_bfs_inv = nullptr; }
-    for (auto& m : h->dU) free_csr(m);
-    for (auto& e : h->dE3) free_ell3(e);
+    h->d_cluster_order = {}; h->d_cluster_inv = {}; h->d_bfs_order = {}; h->d_bfs_inv = {};
     h->dU.clear(); h->dE3.clear();
     h->dU_ready = false;
     h->dU_flagged = false;
@@ -564,53 +539,22 @@ const PatchSet* level0_patches(gmg_handle h, int n) {
     return &p;
 }
 
-void free_level(Level& l) {
-    free_csr(l.dA);
-    free_sell(l.Aoff); free_sell(l.P); free_sell(l.R); free_sell(l.Ain); free_sell(l.Aout);
-    if (l.ain_col16) { (void)dev_free(l.ain_col16); l.ain_col16 = nullptr; }
-    for (int** p : {&l.bc_ptr, &l.bc_mid, &l.bc_col}) { if (*p) (void)dev_free(*p); *p = nullptr; }
-    if (l.bc_val) { (void)dev_free(l.bc_val); l.bc_val = nullptr; }
-    if (l.bc_val32) { (void)dev_free(l.bc_val32); l.bc_val32 = nullptr; }
-    l.use_bcsr = false; l.bc_cap = 0; l.bc_nnz = 0;
-    for (int** q : {&l.ee_ptr, &l.ee_col, &l.ep_ptr}) { if (*q) (void)dev_free(*q); *q = nullptr; }
-    if (l.ep_col) { (void)dev_free(l.ep_col); l.ep_col = nullptr; }
-    for (double** q : {&l.ee_val, &l.ep_val}) { if (*q) (void)dev_free(*q); *q = nullptr; }
-    for (float** q : {&l.ee_val32, &l.ep_val32}) { if (*q) (void)dev_free(*q); *q = nullptr; }
-    l.use_ep = false; l.ee_nnz = l.ep_nnz = 0; l.ep_cap_e = l.ep_cap_l = 0;
-    if (l.d_blk_begin) { (void)dev_free(l.d_blk_begin); l.d_blk_begin = nullptr; }
-    if (l.d_blk_ncolors) { (void)dev_free(l.d_blk_ncolors); l.d_blk_ncolors = nullptr; }
-    if (l.d_row_color) { (void)dev_free(l.d_row_color); l.d_row_color = nullptr; }
-    for (double** p : {&l.diag, &l.x, &l.b, &l.r, &l.tmp}) { if (*p) (void)dev_free(*p); *p = nullptr; }
-    for (float** p : {&l.diag32, &l.x32, &l.b32, &l.r32, &l.tmp32}) { if (*p) (void)dev_free(*p); *p = nullptr; }
-    for (int** q : {&l.src_A, &l.src_diag, &l.src_ee, &l.src_ep}) { if (*q) (void)dev_free(*q); *q = nullptr; }
-    if (l.d_new2old) { (void)dev_free(l.d_new2old); l.d_new2old = nullptr; }
-    if (l.d_old2new) { (void)dev_free(l.d_old2new); l.d_old2new = nullptr; }
-    if (l.d_blk_of_row) { (void)dev_free(l.d_blk_of_row); l.d_blk_of_row = nullptr; }
-}
-
-// the vectors and scalars of the accelerated solve loop (gmg_solver_s::AccelState)
-void drop_accel(gmg_handle h) {
-    auto& a = h->accel;
-    for (double** p : {&a.xk, &a.r, &a.z0, &a.scal, &a.partials}) { if (*p) (void)dev_free(*p); *p = nullptr; }
-    for (int j = 0; j < gmg::kAccelMaxStored; ++j) for (double** p : {&a.zs[j], &a.qs[j]}) { if (*p) (void)dev_free(*p); *p = nullptr; }
-    a.depth = a.d = a.n_pad = 0;
-}
-
 void drop_graphs(gmg_handle h) {
     for (auto& kv : h->graphs) if (kv.second) (void)hipGraphExecDestroy(kv.second);
     h->graphs.clear();
 }
 
+// level 0's vectors are the engine's again: the caller's go (never released: borrowed), the parked ones move back.  (gmg_p2p_load binds the
+// level to its own vectors: nothing is parked then, nothing moves.)
 void unbind_level0(gmg_handle h) {
-    if (h->bound && !h->lv.empty()) { h->lv[0].x = h->own_x0; h->lv[0].b = h->own_b0; h->lv[0].r = h->own_r0; }
-    h->bound = false; h->own_x0 = h->own_b0 = h->own_r0 = nullptr;
+    if (h->bound && !h->lv.empty() && h->lv[0].x.borrowed()) { Level& l = h->lv[0]; l.x = std::move(h->own_x0); l.b = std::move(h->own_b0); l.r = std::move(h->own_r0); }
+    h->bound = false; h->own_x0 = {}; h->own_b0 = {}; h->own_r0 = {};
 }
 
 void lose_live_system(gmg_handle h) { h->live = LiveSystem::none; }
 
 void free_coarse_triangle(gmg_handle h) {
-    for (double** p : {&h->d_tri, &h->d_tri_row, &h->d_tri_col}) if (*p) { (void)dev_free(*p); *p = nullptr; }
-    if (h->d_tri_perm) { (void)dev_free(h->d_tri_perm); h->d_tri_perm = nullptr; }
+    h->d_tri = {}; h->d_tri_row = {}; h->d_tri_col = {}; h->d_tri_perm = {};
     h->tri_n = -1;
 }
 
@@ -619,15 +563,12 @@ void drop_system(gmg_handle h) {
     lose_live_system(h);
     drop_graphs(h);
     unbind_level0(h);
-    drop_accel(h);
+    h->accel = {};
     h->dist_ready = false;
-    for (auto& l : h->lv) free_level(l);
     h->lv.clear();
     h->dcap = 0;
     h->loaded_d = 0;
-    if (h->d_mass) { (void)dev_free(h->d_mass); h->d_mass = nullptr; }
-    if (h->d_minv) { (void)dev_free(h->d_minv); h->d_minv = nullptr; }
-    if (h->d_ainv) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; }
+    h->d_mass = {}; h->d_minv = {}; h->d_ainv = {};
     h->ainv_n = 0;
     free_coarse_triangle(h);
 }

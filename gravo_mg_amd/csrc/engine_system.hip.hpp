@@ -81,7 +81,7 @@ int upload_mass(gmg_handle h) {
     if (l.n != n) return fail(h, GMG_ERR_INVALID, "mass size does not match the system");
     int rc = ensure_stage(h, (size_t)n);
     if (rc) return rc;
-    for (double** p : {&h->d_mass, &h->d_minv}) if (!*p) HIPCHK(dev_malloc((void**)p, sizeof(double) * l.n_pad));
+    for (DevBuf<double>* p : {&h->d_mass, &h->d_minv}) if (!*p && (rc = dev_alloc(h, *p, l.n_pad))) return rc;
     if ((rc = h2d(h, h->d_stage, h->mass.data(), sizeof(double) * (size_t)n))) return rc;
     hipLaunchKernelGGL(gmgk::permute_mass, dim3((l.n_pad + 255) / 256), dim3(256), 0, h->stream, h->d_stage, l.d_new2old, l.n_pad, h->d_mass, h->d_minv);
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -91,13 +91,10 @@ int upload_mass(gmg_handle h) {
 // fp32 twins of the value arrays (mixed precision); `alloc`: (re)allocate them, otherwise they exist with the right sizes
 int refresh_fp32_twins(gmg_handle h, bool alloc) {
     // dst = (float)src[0 .. count); dst gets `cap` floats first when asked to or missing
-    auto twin = [&](const double* src, float*& dst, int64_t count, int64_t cap) -> int {
-        if (alloc || !dst) {
-            if (dst) { (void)dev_free(dst); dst = nullptr; }
-            HIPCHK(dev_malloc((void**)&dst, sizeof(float) * (size_t)cap));
-        }
-        launch_cvt(h, src, dst, (size_t)count);
-        return GMG_OK;
+    auto twin = [&](const double* src, DevBuf<float>& dst, int64_t count, int64_t cap) -> int {
+        int rc = (alloc || !dst) ? dev_alloc(h, dst, (size_t)cap) : GMG_OK;
+        if (rc == GMG_OK) launch_cvt(h, src, dst.get(), (size_t)count);
+        return rc;
     };
     for (int k = 0; k < h->L; ++k) {
         Level& l = h->lv[k];
@@ -149,64 +146,60 @@ int build_coarse_inverse_device(gmg_handle h) {
     std::vector<int4> lev_meta_h(E.lev_q.size()), tile_meta_h(tile_q_h.size());
     for (size_t k = 0; k < E.lev_q.size(); ++k) lev_meta_h[k] = record(E.lev_q[k]);
     for (size_t t = 0; t < tile_q_h.size(); ++t) tile_meta_h[t] = record(tile_q_h[t]);
-    DevTmp<int4> lev_meta, tile_meta;
-    DevTmp<int> rows, lev_ptr, lev_big, tile_ptr;
-    DevTmp<double> vals, tri, dinv;
+    DevBuf<int4> lev_meta, tile_meta;
+    DevBuf<int> rows, lev_ptr, lev_big, tile_ptr;
+    DevBuf<double> vals, tri, dinv;
     int rc;
-    auto up = [&](auto& d, const auto& v) -> int { int r = d.alloc(h, std::max<size_t>(v.size(), 1)); if (r) return r; return v.empty() ? GMG_OK : h2d(h, d.p, v.data(), sizeof(v[0]) * v.size()); };
-    if ((rc = up(lev_meta, lev_meta_h)) || (rc = up(tile_meta, tile_meta_h)) || (rc = up(rows, E.rows)) || (rc = up(lev_ptr, E.lev_ptr)) || (rc = up(lev_big, lev_big_h)) ||
-        (rc = up(tile_ptr, tile_ptr_h)) || (rc = up(vals, E.vals)) || (rc = up(tri, E.tri)) || (rc = up(dinv, E.dinv)))
+    if ((rc = upload(h, lev_meta, lev_meta_h)) || (rc = upload(h, tile_meta, tile_meta_h)) || (rc = upload(h, rows, E.rows)) || (rc = upload(h, lev_ptr, E.lev_ptr)) || (rc = upload(h, lev_big, lev_big_h)) ||
+        (rc = upload(h, tile_ptr, tile_ptr_h)) || (rc = upload(h, vals, E.vals)) || (rc = upload(h, tri, E.tri)) || (rc = upload(h, dinv, E.dinv)))
         return rc;
     std::vector<int> inv_h((size_t)nl);
     for (int i = 0; i < nl; ++i) inv_h[(size_t)E.perm[(size_t)i]] = i;
-    DevTmp<int> perm_d, inv_d;
-    if (!tri_mode && ((rc = up(perm_d, E.perm)) || (rc = up(inv_d, inv_h)))) return rc;
+    DevBuf<int> perm_d, inv_d;
+    if (!tri_mode && ((rc = upload(h, perm_d, E.perm)) || (rc = upload(h, inv_d, inv_h)))) return rc;
     const size_t bytes = sizeof(double) * (size_t)nl * nl;
-    DevTmp<double> X;                                       // the inverse in the factor's numbering
-    if ((rc = X.alloc(h, std::max<size_t>((size_t)nl * nl, 1)))) return rc;
+    DevBuf<double> X;                                       // the inverse in the factor's numbering
+    if ((rc = dev_alloc(h, X, (size_t)nl * nl))) return rc;
     const int lda = (nl + 7) / 8 * 8;
     const int nb = tri_blocks(nl);
     if (tri_mode) {
-        if (h->d_ainv) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; h->ainv_n = 0; }
+        if (h->d_ainv) { h->d_ainv = {}; h->ainv_n = 0; }
         if (h->tri_n != nl) {
             free_coarse_triangle(h);
-            HIPCHK(dev_malloc((void**)&h->d_tri, std::max<size_t>(sizeof(double) * (size_t)tri_block_count(nb) * kTriBlockDoubles, 8)));
-            HIPCHK(dev_malloc((void**)&h->d_tri_row, std::max<size_t>(sizeof(double) * (size_t)tri_row_scratch_doubles(nb), 8)));
-            HIPCHK(dev_malloc((void**)&h->d_tri_col, std::max<size_t>(sizeof(double) * (size_t)tri_col_scratch_doubles(nb), 8)));
-            HIPCHK(dev_malloc((void**)&h->d_tri_perm, std::max<size_t>(sizeof(int) * (size_t)nl, 8)));
+            if ((rc = dev_alloc(h, h->d_tri, (size_t)tri_block_count(nb) * kTriBlockDoubles)) || (rc = dev_alloc(h, h->d_tri_row, (size_t)tri_row_scratch_doubles(nb))) ||
+                (rc = dev_alloc(h, h->d_tri_col, (size_t)tri_col_scratch_doubles(nb))) || (rc = dev_alloc(h, h->d_tri_perm, (size_t)nl))) return rc;
             h->tri_n = nl;
         }
         if (nl > 0 && (rc = h2d(h, h->d_tri_perm, E.perm.data(), sizeof(int) * (size_t)nl))) return rc;
         h->timing["coarse_inverse_bytes"] = (double)(sizeof(double) * (size_t)tri_block_count(nb) * kTriBlockDoubles);
     } else {
         free_coarse_triangle(h);
-        if (h->d_ainv && h->ainv_n != nl) { (void)dev_free(h->d_ainv); h->d_ainv = nullptr; }
-        if (!h->d_ainv) HIPCHK(dev_malloc((void**)&h->d_ainv, std::max<size_t>(sizeof(double) * (size_t)nl * lda, 8)));
+        if ((!h->d_ainv || h->ainv_n != nl) && (rc = dev_alloc(h, h->d_ainv, (size_t)nl * lda))) return rc;
         h->ainv_n = nl; h->ainv_ld = lda;
         h->timing["coarse_inverse_bytes"] = (double)(sizeof(double) * (size_t)nl * lda);
     }
-    HIPCHK(hipMemsetAsync(X.p, 0, bytes, h->stream));
+    HIPCHK(hipMemsetAsync(X, 0, bytes, h->stream));
     gmgs::InvFactor F;
     F.n = nl; F.nq = E.nq; F.nlev = E.nlev;
-    F.lev_meta = lev_meta.p; F.tile_meta = tile_meta.p; F.rows = rows.p; F.lev_ptr = lev_ptr.p; F.lev_big = lev_big.p; F.tile_ptr = tile_ptr.p;
-    F.vals = vals.p; F.tri = tri.p; F.dinv = dinv.p;
+    F.lev_meta = lev_meta; F.tile_meta = tile_meta; F.rows = rows; F.lev_ptr = lev_ptr; F.lev_big = lev_big; F.tile_ptr = tile_ptr;
+    F.vals = vals; F.tri = tri; F.dinv = dinv;
     static_assert(gmgs::kInvChunk == SupernodalLDLT::kChunk, "chunk width of the exported factor");
     const int nt = (nl + width - 1) / width, nm = (nl + 63) / 64;
     h->timing["coarse_inverse_upload_ms"] = ms_since(t0) - h->timing["coarse_inverse_export_ms"];
     if (nl > 0) {
         (void)hipEventRecord(h->ev0, h->stream);
         const dim3 block(64 * gmgs::kInvWaves);
-        if (width == 16) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<16>, dim3(nt), block, 0, h->stream, F, X.p);
-        else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.p);
-        else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.p);
+        if (width == 16) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<16>, dim3(nt), block, 0, h->stream, F, X.get());
+        else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.get());
+        else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.get());
         (void)hipEventRecord(h->ev1, h->stream);
         if (tri_mode) {
-            hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X.p, nl, h->d_tri);
+            hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X, nl, h->d_tri);
         } else {
-            hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.p, nl);
+            hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.get(), nl);
             // ... and into the level's numbering: the product kernel then reads its vectors contiguously
-            if (nl <= 8192) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X.p, (const int*)perm_d.p, (const int*)inv_d.p, nl, h->d_ainv, lda);
-            else hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X.p, (const int*)perm_d.p, nl, h->d_ainv, lda);
+            if (nl <= 8192) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X, (const int*)perm_d, (const int*)inv_d, nl, h->d_ainv, lda);
+            else hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X, (const int*)perm_d, nl, h->d_ainv, lda);
         }
     }
     HIPCHK(hipGetLastError());
@@ -243,18 +236,18 @@ int compute_cheby_bounds(gmg_handle h) {
         if (h->lv[k].Aoff.lpr != 1 || !h->lv[k].Aoff.slice_ptr || !h->lv[k].diag) return fail(h, GMG_ERR_STATE, "the Chebyshev smoother needs the one-lane-per-row operator layout of every level");
         max_blocks = std::max(max_blocks, (h->lv[k].Aoff.n_slices + per_block - 1) / per_block);
     }
-    DevTmp<double> partials, bounds;
+    DevBuf<double> partials, bounds;
     int rc;
-    if ((rc = partials.alloc(h, (size_t)max_blocks)) || (rc = bounds.alloc(h, (size_t)L))) return rc;
+    if ((rc = dev_alloc(h, partials, (size_t)max_blocks)) || (rc = dev_alloc(h, bounds, (size_t)L))) return rc;
     for (int k = 0; k < L; ++k) {
         const Level& l = h->lv[k];
         const int nblk = (l.Aoff.n_slices + per_block - 1) / per_block;
         if (nblk > 0) hipLaunchKernelGGL(gmgs::gershgorin_rows<double>, dim3(nblk), dim3(gmgs::kGershBlock), 0, h->stream, l.Aoff.slice_ptr, (const double*)l.Aoff.val,
-                                         (const double*)l.diag, l.Aoff.n_slices, partials.p);
-        hipLaunchKernelGGL(gmgs::gershgorin_reduce, dim3(1), dim3(gmgs::kGershBlock), 0, h->stream, (const double*)partials.p, nblk, bounds.p + k);
+                                         (const double*)l.diag, l.Aoff.n_slices, partials.get());
+        hipLaunchKernelGGL(gmgs::gershgorin_reduce, dim3(1), dim3(gmgs::kGershBlock), 0, h->stream, (const double*)partials, nblk, bounds + k);
     }
     std::vector<double> host((size_t)L, 0.0);
-    HIPCHK(hipMemcpyAsync(host.data(), bounds.p, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(host.data(), bounds, sizeof(double) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     for (auto it = h->timing.begin(); it != h->timing.end();) it = it->first.rfind("cheby_lambda_l", 0) == 0 ? h->timing.erase(it) : std::next(it);      // (levels of an earlier hierarchy)
     bool moved = false;
@@ -318,9 +311,9 @@ int refresh_system_values(gmg_handle h, int n, const double* val, clk::time_poin
     for (auto it = h->timing.begin(); it != h->timing.end();) it = it->first.rfind("t_", 0) == 0 ? h->timing.erase(it) : std::next(it);
     mark_at(h, t_all, "pattern_key");
     int rc;
-    DevTmp<int> d_err;
-    if ((rc = d_err.alloc(h, 1))) return rc;
-    HIPCHK(hipMemsetAsync(d_err.p, 0, sizeof(int), h->stream));
+    DevBuf<int> d_err;
+    if ((rc = dev_alloc(h, d_err, 1))) return rc;
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->stream));
     h->loaded_d = 0;
     for (int k = 0; k <= L; ++k) h->lv[k].hostA_values = false;          // host copies (if any) keep their pattern only
     if (!values_uploaded && (rc = h2d(h, h->lv[0].dA.val, val, sizeof(double) * (size_t)h->lv[0].nnz))) return rc;
@@ -328,7 +321,7 @@ int refresh_system_values(gmg_handle h, int n, const double* val, clk::time_poin
     auto t0 = clk::now();
     for (int k = 1; k <= L; ++k) {
         Level& lk = h->lv[k];
-        if ((rc = device_rap(h, h->lv[k - 1].dA, h->dU[k - 1], h->dE3[k - 1], lk.dA, lk.A, false, k == L, &lk.nnz, d_err.p, true, k == 1 ? l1_rows_done : (k == 2 ? l2_rows_done : 0)))) return rc < 0 ? rc : GMG_ERR_STATE;
+        if ((rc = device_rap(h, h->lv[k - 1].dA, h->dU[k - 1], h->dE3[k - 1], lk.dA, lk.A, false, k == L, &lk.nnz, d_err, true, k == 1 ? l1_rows_done : (k == 2 ? l2_rows_done : 0)))) return rc < 0 ? rc : GMG_ERR_STATE;
         if (k == L) lk.hostA_values = true;
         mark_at(h, t_all, "rap_l" + std::to_string(k));
     }
@@ -336,10 +329,10 @@ int refresh_system_values(gmg_handle h, int n, const double* val, clk::time_poin
     double ms_factor = 0;
     std::future<bool> factor_done = spawn_coarse_factor(h, true, &ms_factor);
     auto tl = clk::now();
-    for (int k = 0; k < L && rc == GMG_OK; ++k) rc = device_refill_level(h, k, d_err.p);
+    for (int k = 0; k < L && rc == GMG_OK; ++k) rc = device_refill_level(h, k, d_err);
     int herr = 0, herr_aux = 0;
     if (rc == GMG_OK) {
-        (void)hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+        (void)hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream);
         if (l1_rows_done > 0) (void)hipMemcpyAsync(&herr_aux, h->d_aux_err, sizeof(int), hipMemcpyDeviceToHost, h->stream);
         (void)hipStreamSynchronize(h->stream);
         if (herr == 0) herr = herr_aux;
@@ -387,7 +380,6 @@ struct SystemEntry {
     int rc_spec = 1;
     DevCsr early_A0;                  // A_0 in natural numbering, sent up beside the inspection (a handle without a live system)
     AheadColoring ahead;
-    ~SystemEntry() { free_csr(early_A0); }
 };
 
 // A system of the live system's size is most likely the live pattern with new values (the demos' new tau per frame; the first system after
@@ -474,7 +466,7 @@ int enter_system(gmg_handle h, int n, const int* colptr, const int* rowidx, cons
         e.colptr = e.canon.ptr.data(); e.rowidx = e.canon.idx.data(); e.val = e.canon.val.data();
         e.have_key = false;
         e.ahead.cancel();                           // (coloured from rows that are not ascending: no result)
-        free_csr(e.early_A0);                       // (it went up in the caller's storage order)
+        e.early_A0 = {};                            // (it went up in the caller's storage order)
         // (the values went up in the caller's storage order, the resident pattern is canonical: the live system is void, and this
         // matrix takes the full set-up from its canonical copy)
         if (e.speculative) { e.speculative = e.spec_done = false; lose_live_system(h); h->refill_ready = false; }
@@ -573,8 +565,7 @@ public:
         h->timing["setup_h2d"] = ms_h2d;
         const int nblk = std::max(kNormBlocks, grid_for((h->lv[0].n_pad + 63) / 64));        // one partial per four level-0 slices
         if (nblk > h->partial_blocks) {
-            if (h->d_partials) (void)dev_free(h->d_partials);
-            HIPCHK(dev_malloc((void**)&h->d_partials, sizeof(double) * (size_t)nblk * 8));
+            if ((rc = dev_alloc(h, h->d_partials, (size_t)nblk * 8))) return rc;
             h->partial_blocks = nblk;
         }
         return GMG_OK;
@@ -588,14 +579,10 @@ public:
             // Galerkin chain and of the layout builders) and the column maps of the two levels -- goes back to the pool.  A later system pays for
             // them again (no values-only refresh on a partitioned handle); the orderings and the plan stay cached under the pattern digest.
             const bool s1 = h->plan && h->plan->shard1;
-            free_csr(h->lv[0].dA);
-            if (s1) free_csr(h->lv[1].dA);
-            if (!h->dU.empty()) { free_csr(h->dU[0]); free_ell3(h->dE3[0]); }
-            for (int k = 0; k <= (s1 ? 1 : 0); ++k) {
-                Level& lk = h->lv[k];
-                if (lk.d_old2new) { (void)dev_free(lk.d_old2new); lk.d_old2new = nullptr; }
-                if (lk.d_blk_of_row) { (void)dev_free(lk.d_blk_of_row); lk.d_blk_of_row = nullptr; }
-            }
+            h->lv[0].dA = {};
+            if (s1) h->lv[1].dA = {};
+            if (!h->dU.empty()) { h->dU[0] = {}; h->dE3[0] = {}; }
+            for (int k = 0; k <= (s1 ? 1 : 0); ++k) { h->lv[k].d_old2new = {}; h->lv[k].d_blk_of_row = {}; }
             h->pool.trim_large((size_t)4 << 20);   // (the big temporaries go back to the device, not to this handle's pool)
             h->partitioned = true;
         }
@@ -649,7 +636,7 @@ private:
         t0 = clk::now();
         reorder0 = mc && !ord_hit && !blocked0 && wants_locality_reorder(PatternView{n, colptr, rowidx}, h->cfg.reorder_fine);
         if (reorder0) e.ahead.cancel();                // (the level is coloured along another visit order: the loop started on the caller's order is of no use)
-        if (e.early_A0.ptr && device_setup && h->cfg.device_rap) { free_csr(h->lv[0].dA); h->lv[0].dA = e.early_A0; e.early_A0 = DevCsr(); A0_uploaded = true; }
+        if (e.early_A0.ptr && device_setup && h->cfg.device_rap) { h->lv[0].dA = std::move(e.early_A0); e.early_A0 = {}; A0_uploaded = true; }
         // (h->cluster_order is only read once the patches are ready: build_patches may still be writing it)
         const bool have_bfs = (int)h->bfs_order.size() == n, have_cluster = h->patches_ready && (int)h->cluster_order.size() == n;
         h->base_order_choice = (reorder0 && h->patches_ready && have_bfs && !have_cluster) ? 1 : 0;
@@ -678,8 +665,8 @@ private:
     int galerkin_chain() {
         int rc;
         if (device_setup) {
-            rc = d_rap_err.alloc(h, 1);
-            if (rc == GMG_OK) rc = hipMemsetAsync(d_rap_err.p, 0, sizeof(int), h->stream) == hipSuccess ? GMG_OK : GMG_ERR_HIP;
+            rc = dev_alloc(h, d_rap_err, 1);
+            if (rc == GMG_OK) rc = hipMemsetAsync(d_rap_err, 0, sizeof(int), h->stream) == hipSuccess ? GMG_OK : GMG_ERR_HIP;
             if (rc != GMG_OK) return rc;
         }
         device_rap_ok = device_setup && h->cfg.device_rap != 0;
@@ -690,7 +677,7 @@ private:
         for (; k <= L && rc == GMG_OK; ++k) {
             Level& lk = h->lv[k];
             const bool want_pattern = !ord_hit && k < L, want_values = k == L;
-            rc = device_rap(h, h->lv[k - 1].dA, h->dU[k - 1], h->dE3[k - 1], lk.dA, lk.A, want_pattern, want_values, &lk.nnz, d_rap_err.p);
+            rc = device_rap(h, h->lv[k - 1].dA, h->dU[k - 1], h->dE3[k - 1], lk.dA, lk.A, want_pattern, want_values, &lk.nnz, d_rap_err);
             if (rc != GMG_OK) break;
             lk.n = lk.dA.n_outer;
             lk.hostA_pattern = want_pattern || want_values; lk.hostA_values = want_values;
@@ -719,31 +706,30 @@ private:
     }
     // -- layouts built on the device from the raw matrices + orderings (setup_kernels.hip.hpp)
     void device_layouts() {
-        DevTmp<int> d_err;
-        if ((rc_all = d_err.alloc(h, 1)) != GMG_OK) return;
-        (void)hipMemsetAsync(d_err.p, 0, sizeof(int), h->stream);
+        DevBuf<int> d_err;
+        if ((rc_all = dev_alloc(h, d_err, 1)) != GMG_OK) return;
+        (void)hipMemsetAsync(d_err, 0, sizeof(int), h->stream);
         // the coarse levels first: their orderings are short jobs, while level 0's (a sequential greedy colouring of the whole mesh) is the longest
         // host task of the set-up and may still be running
         for (int k = L; k >= 1 && rc_all == GMG_OK; --k) device_ordering(k);
-        int *d_mask0 = nullptr, *d_mask1 = nullptr;
-        struct MaskGuard { int*& a; int*& b; ~MaskGuard() { if (a) (void)dev_free(a); if (b) (void)dev_free(b); } } mask_guard{d_mask0, d_mask1};
+        DevBuf<int> d_mask0, d_mask1;
         bool shard1 = false;
-        if (part && rc_all == GMG_OK) plan_partition(&d_mask0, &d_mask1, &shard1);
+        if (part && rc_all == GMG_OK) plan_partition(d_mask0, d_mask1, &shard1);
         double ms_layout = 0;
         auto tlay = clk::now();
-        for (int k = 1; k < L && rc_all == GMG_OK; ++k) rc_all = device_layout_level(h, k, d_err.p, (k == 1 && shard1) ? d_mask1 : nullptr, nullptr);
+        for (int k = 1; k < L && rc_all == GMG_OK; ++k) rc_all = device_layout_level(h, k, d_err, (k == 1 && shard1) ? d_mask1.get() : nullptr, nullptr);
         if (part && shard1 && rc_all == GMG_OK && !h->lv[1].use_ep) { rc_all = GMG_ERR_UNSUPPORTED; err_all = "level 1 cannot run the entry-parallel block sweep (a block is too large for its LDS buffers): create the handle with dist_shard_levels = 1"; }
         ms_layout += ms_since(tlay);
         early_inverse();
         if (rc_all == GMG_OK && !part) device_ordering(0);
         tlay = clk::now();
-        if (rc_all == GMG_OK) rc_all = device_layout_level(h, 0, d_err.p, part ? d_mask0 : nullptr, (part && shard1) ? d_mask1 : nullptr);
+        if (rc_all == GMG_OK) rc_all = device_layout_level(h, 0, d_err, part ? d_mask0.get() : nullptr, (part && shard1) ? d_mask1.get() : nullptr);
         ms_layout += ms_since(tlay);
         h->timing["setup_device_layout"] = ms_layout;
         mark("device_layout");
         if (rc_all != GMG_OK) return;
         int herr = 0;
-        (void)hipMemcpyAsync(&herr, d_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+        (void)hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream);
         (void)hipStreamSynchronize(h->stream);
         if (herr == 2) { rc_all = GMG_ERR_NUMERIC; err_all = "system matrix has a missing or zero diagonal entry"; }
         else if (herr != 0 && part) { rc_all = GMG_ERR_UNSUPPORTED; err_all = "rows too long for the device layout builder: a partitioned set-up has no host fallback"; }
@@ -758,7 +744,7 @@ private:
     }
     // A partitioned set-up (gmg_dist_partition) lays out this rank's rows of levels 0 / 1 only: it needs the partition plan -- hence both orderings
     // -- before the first layout; everybody else's rows are masked out of the row maps the builders read
-    void plan_partition(int** d_mask0, int** d_mask1, bool* shard1) {
+    void plan_partition(DevBuf<int>& d_mask0, DevBuf<int>& d_mask1, bool* shard1) {
         device_ordering(0);
         auto tp = clk::now();
         const LevelOrdering& o0 = h->lv[0].ord;
@@ -802,7 +788,7 @@ private:
         for (int k = 0; k <= L && rc_all == GMG_OK; ++k) {
             if (!ordering_arrived(k)) break;
             auto tu = clk::now();
-            if ((rc_all = upload(h, &h->lv[k].d_new2old, h->lv[k].ord.new2old))) break;
+            if ((rc_all = upload(h, h->lv[k].d_new2old, h->lv[k].ord.new2old))) break;
             ms_h2d += ms_since(tu);
             if (k == L) break;
             op_done[k].get();
@@ -822,24 +808,24 @@ private:
         Level& l = h->lv[k];
         const LevelStage& st = stage[k];
         int rc;
-        if ((rc = upload_sell(h, l.Aoff, st.sa)) || (rc = upload(h, &l.diag, st.dg))) return rc;
+        if ((rc = upload_sell(h, l.Aoff, st.sa)) || (rc = upload(h, l.diag, st.dg))) return rc;
         if (!l.ord.blocked) return GMG_OK;
         if (st.use_ep) {
             l.use_ep = true;
             l.ee_nnz = st.bc.ptr[l.n_pad]; l.ep_nnz = st.bin.ptr[l.n_pad];
             l.ep_cap_e = (st.bc.max_block_entries + 63) / 64 * 64; l.ep_cap_l = std::max(st.bin.max_block_entries, 1);
-            if ((rc = upload(h, &l.ee_ptr, st.bc.ptr)) || (rc = upload(h, &l.ee_col, st.bc.col)) || (rc = upload(h, &l.ee_val, st.bc.val)) ||
-                (rc = upload(h, &l.ep_ptr, st.bin.ptr)) || (rc = upload(h, &l.ep_col, st.ep16)) || (rc = upload(h, &l.ep_val, st.bin.val))) return rc;
+            if ((rc = upload(h, l.ee_ptr, st.bc.ptr)) || (rc = upload(h, l.ee_col, st.bc.col)) || (rc = upload(h, l.ee_val, st.bc.val)) ||
+                (rc = upload(h, l.ep_ptr, st.bin.ptr)) || (rc = upload(h, l.ep_col, st.ep16)) || (rc = upload(h, l.ep_val, st.bin.val))) return rc;
         } else {
-            if ((rc = upload_sell(h, l.Ain, st.sin)) || (rc = upload_sell(h, l.Aout, st.sout)) || (rc = upload(h, &l.ain_col16, st.c16))) return rc;
+            if ((rc = upload_sell(h, l.Ain, st.sin)) || (rc = upload_sell(h, l.Aout, st.sout)) || (rc = upload(h, l.ain_col16, st.c16))) return rc;
             if (st.use_bcsr) {
                 l.use_bcsr = true;
                 l.bc_cap = (st.bc.max_block_entries + 63) / 64 * 64;
                 l.bc_nnz = st.bc.ptr[l.n_pad];
-                if ((rc = upload(h, &l.bc_ptr, st.bc.ptr)) || (rc = upload(h, &l.bc_mid, st.bc.mid)) || (rc = upload(h, &l.bc_col, st.bc.col)) || (rc = upload(h, &l.bc_val, st.bc.val))) return rc;
+                if ((rc = upload(h, l.bc_ptr, st.bc.ptr)) || (rc = upload(h, l.bc_mid, st.bc.mid)) || (rc = upload(h, l.bc_col, st.bc.col)) || (rc = upload(h, l.bc_val, st.bc.val))) return rc;
             }
         }
-        if ((rc = upload(h, &l.d_blk_begin, l.ord.blk_begin)) || (rc = upload(h, &l.d_blk_ncolors, l.ord.blk_ncolors)) || (rc = upload(h, &l.d_row_color, l.ord.row_color))) return rc;
+        if ((rc = upload(h, l.d_blk_begin, l.ord.blk_begin)) || (rc = upload(h, l.d_blk_ncolors, l.ord.blk_ncolors)) || (rc = upload(h, l.d_row_color, l.ord.row_color))) return rc;
         return GMG_OK;
     }
     void spawn_level(int k) {
@@ -942,7 +928,7 @@ private:
         h->timing["setup_wait_ordering"] += ms_since(tw);
         mark("ordering_ready_l" + std::to_string(k));
         if (h->lv[k].ord.n_colors > kMaxColors) { rc_all = GMG_ERR_UNSUPPORTED; err_all = "more than " + std::to_string(kMaxColors) + " colours on level " + std::to_string(k); return; }
-        rc_all = upload(h, &h->lv[k].d_new2old, h->lv[k].ord.new2old);
+        rc_all = upload(h, h->lv[k].d_new2old, h->lv[k].ord.new2old);
     }
     void wait_lhs() { if (lhs_copied.valid()) lhs_copied.wait(); }
     void mark(const std::string& what) { mark_at(h, t_all, what); }
@@ -976,7 +962,7 @@ private:
     std::atomic<int> colored_ahead{0};             // the level-0 ordering took the colouring made ahead of the verdict (AheadColoring)
     double ms_lhs_copied = 0, ms_h2d = 0;
     clk::time_point t0;
-    DevTmp<int> d_rap_err;
+    DevBuf<int> d_rap_err;
     int rc_all = GMG_OK;
     std::string err_all;
 };
