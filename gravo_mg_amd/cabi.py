@@ -157,6 +157,7 @@ INTERNAL_SIGNATURES = {
                                            C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), _ip, _dp]),
     "gmg_hierarchy_debug_row_kinds": (C.c_int, [_vp, C.c_int, _ip]),
     "gmg_host_galerkin": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp]),
+    "gmg_debug_device_galerkin": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _dp, C.c_int, _ip, _ip, _dp, C.c_int64, _ip, _ip, _dp, _dp, _ip]),
     "gmg_host_plan_level": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_ubyte)]),
     "gmg_host_fine_block_rule": (C.c_int, [C.c_int, _ip, _ip, _dp, _ip, _ip]),
@@ -833,9 +834,39 @@ def rccl_unique_id() -> bytes:
     return buf.raw
 
 
-def host_galerkin(A, U) -> sp.csc_matrix:
-    """Ac = U^T A U on the host (the product engine's RAP, exposed for parity tests)."""
-    a, u = _csc(A), _csc(U)
+def device_galerkin(eng: "Engine", A, U, val2=None):
+    """Ac = U^T A U by the device kernel, through the set-up's own code on arrays of its own (gmg_debug_device_galerkin; the engine lends its
+    stream and pool).  A and U go in AS STORED (column order, stored zeros).  Returns (status, C, values2): status 0 and the product, or
+    status 1 and None when the device declines (a coarse row with too many distinct columns, a U row with more than 3 entries); values2: the
+    values of the numeric pass alone after `val2` (a second value array on A's pattern) replaced A's values, or None."""
+    a, u = _csc_layout(A), _csc_layout(U)
+    nc = u.shape[1]
+    v2 = None if val2 is None else np.ascontiguousarray(val2, dtype=np.float64)
+    if v2 is not None and v2.shape != a.data.shape:
+        raise ValueError("val2 must have one value per stored entry of A")
+    colptr, status = np.zeros(nc + 1, np.int32), C.c_int(-1)
+    cap = a.nnz + nc
+    for attempt in range(2):      # (the product rarely has more entries than A; when it has, c_colptr says how many)
+        rowidx, val = np.empty(max(cap, 1), np.int32), np.empty(max(cap, 1), np.float64)
+        out2 = np.empty(max(cap, 1), np.float64) if v2 is not None else None
+        rc = lib().gmg_debug_device_galerkin(eng._h, a.shape[0], _pi(a.indptr), _pi(a.indices), _pd(a.data), _pd(v2) if v2 is not None else None, nc,
+                                             _pi(u.indptr), _pi(u.indices), _pd(u.data), cap, _pi(colptr), _pi(rowidx), _pd(val),
+                                             _pd(out2) if out2 is not None else None, C.byref(status))
+        if rc == GMG_ERR_INVALID and attempt == 0 and int(colptr[nc]) > cap:
+            cap = int(colptr[nc])
+            continue
+        eng._chk(rc)
+        break
+    if status.value != 0:
+        return status.value, None, None
+    nnz = int(colptr[nc])
+    return 0, sp.csc_matrix((val[:nnz].copy(), rowidx[:nnz].copy(), colptr), shape=(nc, nc)), (out2[:nnz].copy() if out2 is not None else None)
+
+
+def host_galerkin(A, U, as_stored: bool = False) -> sp.csc_matrix:
+    """Ac = U^T A U on the host (the product engine's RAP, exposed for parity tests).  as_stored: A and U go in as they are stored (column
+    order, stored zeros, repeats) instead of in canonical form."""
+    a, u = (_csc_layout(A), _csc_layout(U)) if as_stored else (_csc(A), _csc(U))
     nc = u.shape[1]
     colptr = np.zeros(nc + 1, np.int32)
     rc = lib().gmg_host_galerkin(a.shape[0], _pi(a.indptr), _pi(a.indices), _pd(a.data), nc, _pi(u.indptr), _pi(u.indices), _pd(u.data),

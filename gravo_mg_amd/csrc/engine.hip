@@ -1470,6 +1470,54 @@ int gmg_host_galerkin(int n, const int* a_colptr, const int* a_rowidx, const dou
     return GMG_OK;
 } GMG_CATCH_0
 
+// Test access to the device Galerkin product (gravomg_hip_internal.h): the set-up's own upload_csr_raw / build_ell3 / device_rap on local
+// DevCsr / DevEll3 objects.  Nothing is launched from here, and of the handle only the stream, the pool and the bounce buffers are used.
+int gmg_debug_device_galerkin(gmg_handle h, int n, const int* a_colptr, const int* a_rowidx, const double* a_val, const double* a_val2, int n_coarse,
+                              const int* u_colptr, const int* u_rowidx, const double* u_val, int64_t cap, int* c_colptr, int* c_rowidx, double* c_val,
+                              double* c_val2, int* status) try {
+    NEED_DEVICE();
+    if (n <= 0 || n_coarse <= 0 || cap < 0 || !a_colptr || !a_rowidx || !a_val || !u_colptr || !u_rowidx || !u_val || !c_colptr || !c_rowidx || !c_val || !status ||
+        (a_val2 && !c_val2)) return fail(h, GMG_ERR_INVALID, "bad arguments");
+    // every index the kernels follow, checked once: they read without bounds
+    if (a_colptr[0] != 0 || u_colptr[0] != 0) return fail(h, GMG_ERR_INVALID, "column pointers must start at 0");
+    for (int i = 0; i < n; ++i) if (a_colptr[i + 1] < a_colptr[i]) return fail(h, GMG_ERR_INVALID, "column pointers of A decrease");
+    for (int c = 0; c < n_coarse; ++c) if (u_colptr[c + 1] < u_colptr[c]) return fail(h, GMG_ERR_INVALID, "column pointers of U decrease");
+    for (int q = 0; q < a_colptr[n]; ++q) if (a_rowidx[q] < 0 || a_rowidx[q] >= n) return fail(h, GMG_ERR_INVALID, "row index of A out of range");
+    for (int q = 0; q < u_colptr[n_coarse]; ++q) if (u_rowidx[q] < 0 || u_rowidx[q] >= n) return fail(h, GMG_ERR_INVALID, "row index of U out of range");
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, GMG_ERR_HIP, "hipSetDevice failed");
+    DevCsr dA, dU, dC;
+    DevEll3 e3;
+    DevBuf<int> d_err;
+    Compressed C;
+    int rc, herr = 0;
+    if ((rc = dev_alloc(h, d_err, 1))) return rc;
+    HIPCHK(hipMemsetAsync(d_err, 0, sizeof(int), h->stream));
+    if ((rc = upload_csr_raw(h, dA, n, a_colptr, a_rowidx, a_val)) || (rc = upload_csr_raw(h, dU, n_coarse, u_colptr, u_rowidx, u_val)) ||
+        (rc = build_ell3(h, e3, dU, n, d_err))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    HIPCHK(hipMemcpyAsync(&herr, d_err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));      // the caller's arrays have been consumed
+    *status = 0;
+    if (herr) { *status = 1; return GMG_OK; }     // a U row with more than 3 entries (ensure_device_transfers: dU_flagged): rap_rows is not launched
+    int64_t nnz = 0;
+    rc = device_rap(h, dA, dU, e3, dC, C, true, true, &nnz, d_err);
+    if (rc == 1) { *status = 1; return GMG_OK; }  // a coarse row overflows the hash set: the set-up goes on with the host product
+    if (rc) return rc;
+    std::memcpy(c_colptr, C.ptr.data(), sizeof(int) * ((size_t)n_coarse + 1));
+    if (nnz > cap) return fail(h, GMG_ERR_INVALID, "the product has " + std::to_string(nnz) + " entries: more than the caller's capacity (c_colptr is filled)");
+    if (nnz) { std::memcpy(c_rowidx, C.idx.data(), sizeof(int) * (size_t)nnz); std::memcpy(c_val, C.val.data(), sizeof(double) * (size_t)nnz); }
+    if (a_val2) {
+        // the values-only refresh: new values into the resident A, the numeric pass alone on the pattern at hand (refresh_system_values)
+        Compressed C2;
+        if ((rc = h2d(h, dA.val, a_val2, sizeof(double) * (size_t)a_colptr[n]))) { (void)hipStreamSynchronize(h->stream); return rc; }
+        rc = device_rap(h, dA, dU, e3, dC, C2, false, true, &nnz, d_err, true);
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (rc) return rc < 0 ? rc : fail(h, GMG_ERR_STATE, "the numeric pass declined a pattern the product was made on");
+        if ((int64_t)C2.val.size() != nnz) return fail(h, GMG_ERR_STATE, "the numeric pass returned another number of entries");
+        if (nnz) std::memcpy(c_val2, C2.val.data(), sizeof(double) * (size_t)nnz);
+    }
+    return GMG_OK;
+} GMG_CATCH_H
+
 int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const double* val, int mode, int block_rows, int sigma, int64_t* info,
                         int* new2old, int* color_begin, int* blk_begin, unsigned char* row_color) try {
     if (n <= 0 || !colptr || !rowidx || !val || mode < 0 || mode > 4) return GMG_ERR_INVALID;

@@ -350,6 +350,7 @@ int refresh_system_values(gmg_handle h, int n, const double* val, clk::time_poin
     if ((rc = finish_system(h, n, ms_factor, false, false, false))) return rc;
     h->timing["setup_ordering_cached"] = 1.0;
     h->timing["setup_values_only"] = 1.0;
+    h->timing["rap_device_levels"] = (double)L;      // every level by the numeric pass of rap_rows
     h->timing["setup_ordering"] = 0.0; h->timing["setup_sell"] = 0.0; h->timing["setup_wait_ordering"] = 0.0;
     for (int k = 0; k <= L; ++k) h->timing["setup_ordering_l" + std::to_string(k)] = 0.0;
     stamp_done(h, t_all);
@@ -670,6 +671,7 @@ private:
             if (rc != GMG_OK) return rc;
         }
         device_rap_ok = device_setup && h->cfg.device_rap != 0;
+        h->timing["rap_device_levels"] = 0.0;      // levels 1 .. L whose operator rap_rows produced (gravomg_hip.h)
         if (!device_rap_ok) return host_chain(1);
         rc = A0_uploaded ? GMG_OK : upload_csr_raw(h, h->lv[0].dA, n, colptr, rowidx, val);
         mark("upload_A0");
@@ -682,6 +684,7 @@ private:
             lk.n = lk.dA.n_outer;
             lk.hostA_pattern = want_pattern || want_values; lk.hostA_values = want_values;
             spawn_level(k);
+            h->timing["rap_device_levels"] = (double)k;
             mark("rap_l" + std::to_string(k));
         }
         if (rc != 1) return rc;

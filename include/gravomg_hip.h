@@ -198,6 +198,9 @@ int gmg_set_mass(gmg_handle h, int n, const double* mass_diag);
  * (recognised by a 128-bit digest of colptr/rowidx) only refreshes values in place -- numeric Galerkin passes, layout
  * refill, numeric LDL^T; timing key "setup_values_only" = 1 -- and a matrix with a pattern seen before on this handle
  * reuses the orderings ("setup_ordering_cached" = 1).  Results are those of a fresh handle in every case.
+ * "rap_device_levels" (read-only, changes nothing): how many of the levels 1 .. L of the live system got their operator from the device
+ * Galerkin kernel in the last call -- 0 with device_rap = 0, device_setup = 0 or a prolongation row of more than 3 entries, k - 1 when
+ * level k had more distinct columns in a row than the kernel holds and the chain went on with the host product, L after a values-only refresh.
  * A call that FAILS (GMG_ERR_INVALID for an index out of range, GMG_ERR_NUMERIC for a zero diagonal / pivot, ...) leaves the handle WITHOUT a
  * system: a matrix of the live system's size has its values uploaded over the resident A_0 -- and the refresh started -- while the pattern is
  * still being inspected, so the previous system does not survive a rejected call; the next solve returns GMG_ERR_STATE until a gmg_set_system

@@ -52,6 +52,20 @@ int gmg_host_galerkin(int n, const int* a_colptr, const int* a_rowidx, const dou
                       int n_coarse, const int* u_colptr, const int* u_rowidx, const double* u_val,
                       int* c_colptr, int* c_rowidx, double* c_val);
 
+/* The DEVICE Galerkin product Ac = U^T A U (csrc/setup_kernels.hip.hpp::rap_rows) on arrays the caller builds by hand, through the code the
+ * set-up runs -- upload of A and U, the by-row regrouping of U, count pass / prefix sum / fill pass -- on objects of its own: the handle lends
+ * its stream and its pool and is otherwise left alone (hierarchy, system and timing keys untouched; no kernel launch that the set-up does not
+ * make).  A: n x n, CSC as stored (unsorted columns and stored zeros are taken as they are), symmetric pattern; U: n x n_coarse, CSC.
+ * Every index is checked (GMG_ERR_INVALID).  Out: *status = 0 and the product (c_colptr n_coarse + 1, c_rowidx / c_val of `cap` entries;
+ * GMG_ERR_INVALID with c_colptr filled when the product has more), or *status = 1 when the device declines as it does in the set-up: a coarse
+ * row with more distinct columns than the kernel's hash set holds, or a row of U with more than 3 entries (the product kernel is then not
+ * launched at all).  a_val2 (optional): a second value array on the pattern of A.  After the product it is written over the resident values
+ * and the numeric pass alone runs on the pattern at hand (what a values-only gmg_set_system does); its values go to c_val2 (cap entries).
+ * GMG_ERR_NO_DEVICE without a HIP device. */
+int gmg_debug_device_galerkin(gmg_handle h, int n, const int* a_colptr, const int* a_rowidx, const double* a_val, const double* a_val2, int n_coarse,
+                              const int* u_colptr, const int* u_rowidx, const double* u_val, int64_t cap, int* c_colptr, int* c_rowidx, double* c_val,
+                              double* c_val2, int* status);
+
 /* Host-only view of the device layout planner (colouring / block growing / SELL-64), for CPU tests of the
  * host logic.  mode 0: colour-major ordering (exact multicolour Gauss-Seidel), mode 1: block ordering
  * (block-hybrid Gauss-Seidel, `block_rows` rows per block), mode 2: mode 0 with the locality reordering forced (rows of a colour in breadth-first
