@@ -337,6 +337,7 @@ public:
         else if (key == "dist_exchange") c.dist_exchange = (int)value;
         else if (key == "inner_precision") c.inner_precision = (int)value;
         else if (key == "accelerate") c.accelerate = (int)value;
+        else if (key == "fold_head") c.fold_head = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

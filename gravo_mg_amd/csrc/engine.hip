@@ -137,6 +137,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->prepare_structure = 1;
     cfg->fuse_restrict_sweep = 1;
     cfg->speculate_head = 1;
+    cfg->fold_head = 1;
     cfg->uniform_slices = 1;
     cfg->color_ahead = 1;
     cfg->dist_exchange = 0;
@@ -615,7 +616,7 @@ namespace {
 // every cycle a CycleWatch and whether the cycle's head is in the stream: its own locals, so nothing of them outlives it.
 inline bool loop_enqueues_heads(gmg_handle h, int d, bool wanted) {
     if (!wanted || !head_eligible(h, d)) return false;
-    h->timing["heads_enqueued"] += 0.0; h->timing["head_decision_differs"] += 0.0;
+    h->timing["heads_enqueued"] += 0.0; h->timing["head_decision_differs"] += 0.0; h->timing["heads_folded"] += 0.0;
     return true;
 }
 }  // namespace
@@ -633,12 +634,14 @@ int gmg_run_cycles(gmg_handle h, int n_cycles, int stop_type, double* residues) 
     // as in the solve loop -- there the check's reduction decides on the device whether that launch does anything, solve_common)
     const bool heads = loop_enqueues_heads(h, d, stop_type >= 0);
     CycleWatch watch{0, 0.0, stop_type, 0};
-    bool head_done = false;          // this cycle's first colour launch is in the stream
+    int head_done = HEAD_NONE;       // this cycle's first colour launch is in the stream (HEAD_FOLDED: its first two)
     for (int i = 0; i < n_cycles; ++i) {
         watch.cycles_done = i + 1;
+        const bool head = heads && i + 1 < n_cycles;
+        watch.fold = head && fold_eligible(h, d);       // (the check then also computes the head's values: asked anew every cycle)
         if ((rc = vcycle_resident(h, d, stop_type, head_done, heads ? &watch : nullptr))) return rc;
         if (stop_type >= 0) {
-            head_done = heads && i + 1 < n_cycles && enqueue_head(h, d);
+            head_done = head ? enqueue_head(h, d, watch.fold) : HEAD_NONE;
             if ((rc = wait_norm(h))) return rc;
             if (residues) residues[i] = norm_from_sums(h->h_norm, d, stop_type);
         }
@@ -744,16 +747,19 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     // the device are hidden behind that launch.  The loop follows the device's word.
     const bool heads = loop_enqueues_heads(h, d, accel == 0);
     CycleWatch watch{1, tol, stop_type, 0};
-    bool head_done = false;          // the coming cycle's first colour launch is in the stream (and found the word set)
+    // gmg_config::fold_head: the check computes the head's values too and the launch enqueued behind it is the second colour launch, which
+    // commits them (engine_cycle.hip.hpp::fold_eligible) -- a stopped iteration still returns at once, x the iterate that was checked.
+    int head_done = HEAD_NONE;       // the coming cycle's first colour launch is in the stream (HEAD_FOLDED: its first two) and found the word set
     auto plain_step = [&](const SolveRule& rule, double& residue, int& device_go) -> int {
         watch.cycles_done = rule.cycles + 1;
         const bool head = heads && rule.cycles + 2 <= rule.max_iter;          // (a cycle after this one is allowed)
+        watch.fold = head && fold_eligible(h, d);                             // (asked anew every iteration)
         if ((rc = vcycle_resident(h, d, stop_type, head_done, heads ? &watch : nullptr))) return rc;
-        head_done = head && enqueue_head(h, d);
+        head_done = head ? enqueue_head(h, d, watch.fold) : HEAD_NONE;
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
         if (head) device_go = __atomic_load_n(h->h_flag + 1, __ATOMIC_ACQUIRE) != 0;
-        if (device_go == 0) head_done = false;                  // that launch found the word cleared and returned
+        if (device_go == 0) head_done = HEAD_NONE;              // that launch found the word cleared and returned
         return GMG_OK;
     };
     int verdict;

@@ -69,7 +69,7 @@ template <class T>
 struct SmoothAsk {
     bool from_zero = false;       // the iterate is the zero vector: the first block sweep takes no input (and the caller skipped the memset)
     bool first_done = false;      // ... and the restriction's launch already ran that sweep: its result is in tmp (restrict_into)
-    bool head_done = false;       // level 0: the first colour launch is already in the stream (enqueue_head)
+    int head_done = 0;            // level 0: the first colour launch is already in the stream (enqueue_head; HEAD_FOLDED: the first two)
     T* res_out = nullptr;         // level-0 pre-smoothing: where the last colour launch may write the residual of its rows (fold_residual) ...
     bool res_il = false;          // ... as an interleaved multi-vector
     int norm_type = -1;           // level-0 post-smoothing: the residual check the cycle ends with, which the last colour launch may join (fold_norm)
@@ -154,25 +154,58 @@ inline bool head_eligible(gmg_handle h, int d) {
            !h->lv[0].ord.blocked && h->lv[0].ord.n_colors >= 2 && first_color(h->lv[0]) >= 0 && first_color(h->lv[0]) < h->lv[0].ord.n_colors - 1 && d >= 1 && d <= 4 &&
            !h->partitioned && h->part_world <= 1 && h->d_watch && !h->prof_on;
 }
-// (returns true: the head is in the stream, what the caller hands to the next cycle)
-inline bool enqueue_head(gmg_handle h, int d) {
+// The folded head (gmg_config::fold_head): the residual check in front of the head computes the first colour's update as well -- it holds every
+// operand -- and stores it to the side vector (residual_norm_slices_head); the launch enqueued ahead of the decision is then the SECOND colour
+// launch, which gathers the first colour's columns from the side vector and commits it to x (gs_color_commit).  One launch and one pass over
+// the first colour's rows less per cycle; speculation stays one launch deep.  Asked per iteration (wait_flag may switch polling off in
+// mid-solve): where today's head goes, with a second non-empty colour class whose launch of the first pre-sweep is a plain one (not the
+// sweep's last launch, which carries the residual: fold_residual) and the side vector in place.
+inline int second_color(const Level& l) {
+    for (int c = first_color(l) + 1; c > 0 && c < l.ord.n_colors; ++c)
+        if (l.ord.color_begin[c + 1] / 64 > l.ord.color_begin[c] / 64) return c;
+    return -1;
+}
+inline bool fold_eligible(gmg_handle h, int d) {
+    if (!h->cfg.fold_head || h->cfg.accelerate != 0 || !head_eligible(h, d)) return false;
+    const Level& l = h->lv[0];
+    const int c1 = first_color(l), c2 = second_color(l);
+    return c2 > 0 && (c2 < l.ord.n_colors - 1 || h->cfg.pre_iters >= 2) && l.xh &&
+           l.xh_rows == (l.ord.color_begin[c1 + 1] / 64 - l.ord.color_begin[c1] / 64) * 64 && d <= h->dcap;
+}
+// What of the coming cycle is in the stream, enqueued ahead of the loop's decision: nothing, its first colour launch, or (folded) its first
+// two -- what the caller hands to that cycle (vcycle_resident's head_done -> SmoothAsk::head_done)
+enum { HEAD_NONE = 0, HEAD_FIRST = 1, HEAD_FOLDED = 2 };
+// (folded: the check in front was asked for the side vector, CycleWatch::fold)
+inline int enqueue_head(gmg_handle h, int d, bool folded = false) {
     Level& l = h->lv[0];
     const int c = first_color(l);
-    launch_gs_color<double>(h, l, 0, d, l.ord.color_begin[c] / 64, l.ord.color_begin[c + 1] / 64, level_omega<double>(h, l), nullptr, reinterpret_cast<const int*>(h->d_watch + 1));
+    const int* go = reinterpret_cast<const int*>(h->d_watch + 1);
     h->timing["heads_enqueued"] += 1.0;
-    return true;
+    if (!folded) {
+        launch_gs_color<double>(h, l, 0, d, l.ord.color_begin[c] / 64, l.ord.color_begin[c + 1] / 64, level_omega<double>(h, l), nullptr, go);
+        return HEAD_FIRST;
+    }
+    const int c2 = second_color(l);
+    const int hb = l.ord.color_begin[c] / 64, he = l.ord.color_begin[c + 1] / 64, sb = l.ord.color_begin[c2] / 64, se = l.ord.color_begin[c2 + 1] / 64;
+    const int n_work = grid_for(se - sb), n_copy = ((he - hb) * 32 + gmgk::kBlock - 1) / gmgk::kBlock;      // (the commit moves two rows per lane)
+    DISPATCH_D(d, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::gs_color_commit<D, C16>), dim3(n_work + n_copy), dim3(gmgk::kBlock), 0, h->stream,
+                                     l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b, l.x, l.n_pad, sb, se, n_work, level_omega<double>(h, l), l.Aoff.col16,
+                                     l.Aoff.win_base, l.Aoff.c16_arg(), l.xh.get(), hb, he, go)));
+    h->timing["heads_folded"] += 1.0;
+    return HEAD_FOLDED;
 }
 
 template <class T>
 SmoothDone<T> launch_gs_sweeps(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask) {
     SmoothDone<T> done;
-    const int c_head = ask.head_done ? first_color(l) : -1;      // (the first launch of this cycle is already in the stream: enqueue_head)
+    // (the first launch of this cycle is already in the stream: enqueue_head -- the first two where the head was folded)
+    const int c_head = ask.head_done ? first_color(l) : -1, c_head2 = ask.head_done == HEAD_FOLDED ? second_color(l) : -1;
     for (int it = 0; it < iters; ++it)
         for_col_chunks(d, [&](int c0, int dc) {
             for (int c = 0; c < l.ord.n_colors; ++c) {
                 int sb = l.ord.color_begin[c] / 64, se = l.ord.color_begin[c + 1] / 64;
                 if (se <= sb) continue;
-                if (it == 0 && c0 == 0 && c == c_head) continue;
+                if (it == 0 && c0 == 0 && (c == c_head || c == c_head2)) continue;
                 const bool last_launch = it == iters - 1 && c == l.ord.n_colors - 1;
                 if (const int nblk = fold_norm<T>(h, l, d, last_launch, sb, se, ask.norm_type)) { done.norm_blocks = nblk; continue; }
                 if (const int from = fold_residual<T>(h, l, d, last_launch, sb, se, ask.res_out, ask.res_il)) { done.res_from = from; continue; }
@@ -495,7 +528,8 @@ int wait_norm(gmg_handle h) {
 
 // What the check's reduction needs to take the loop's decision on the device (gmgk::SolveWatch): mode 0 a fixed number of cycles, 1 the rule of
 // solve_rule.hpp; cycles done including this one.  The loops that enqueue heads hand one to vcycle_resident with every cycle; nobody else does.
-struct CycleWatch { int mode; double tol; int type; int cycles_done; };
+// fold: the check also stores the next cycle's first colour update to level 0's side vector (fold_eligible; the caller then enqueues the folded head).
+struct CycleWatch { int mode; double tol; int type; int cycles_done; bool fold = false; };
 
 // the reduction of one group of <= 4 columns: into h_norm + flag when polled, into d_norm (+ a copy later) otherwise
 // (partials: whose block sums -- the norm kernels' by default; decide: also take the loop's decision, see CycleWatch)
@@ -521,10 +555,20 @@ int launch_norm(gmg_handle h, int d, int type, int folded = 0, const CycleWatch*
     const int n_slices = folded ? l.ord.color_begin[l.ord.n_colors - 1] / 64 : l.Aoff.n_slices;
     const int nblk = norm_grid(n_slices);                // one slice per wave, like the residual SpMV; one partial per block of 16
     const bool poll = polled(h);
+    // (decide->fold: the same sums, and the next cycle's first colour update into level 0's side vector -- one group of columns, fold_eligible;
+    // the first colour's slices lie in front of the last colour's, inside n_slices)
+    const int c_head = decide && decide->fold && d <= 4 ? first_color(l) : -1;
     for_col_chunks(d, [&](int c0, int dc) {
-        DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices<D, 0, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
-                                          l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * l.n_pad, l.x + (size_t)c0 * l.n_pad, w,
-                                          l.n_pad, n_slices, (float*)nullptr, h->d_partials, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
+        if (c_head >= 0) {
+            DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices_head<D, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
+                                              l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b.get(), l.x.get(), w, l.n_pad, n_slices, h->d_partials.get(), l.Aoff.col16,
+                                              l.Aoff.win_base, l.Aoff.c16_arg(), l.xh.get(), l.ord.color_begin[c_head] / 64, l.ord.color_begin[c_head + 1] / 64,
+                                              level_omega<double>(h, l))));
+        } else {
+            DISPATCH_D(dc, DISPATCH_C16(l.Aoff.c16_sel(), hipLaunchKernelGGL((gmgk::residual_norm_slices<D, 0, C16>), dim3(nblk), dim3(gmgk::kNormWaves * 64), 0, h->stream,
+                                              l.Aoff.slice_ptr, l.Aoff.col, l.Aoff.val, l.diag, l.b + (size_t)c0 * l.n_pad, l.x + (size_t)c0 * l.n_pad, w,
+                                              l.n_pad, n_slices, (float*)nullptr, h->d_partials, l.Aoff.col16, l.Aoff.win_base, l.Aoff.c16_arg())));
+        }
         launch_reduce(h, nblk + folded, dc, c0, c0 + 4 >= d, nullptr, decide);
     });
     if (!poll) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
@@ -550,6 +594,17 @@ int ensure_vectors(gmg_handle h, int d) {
         int rc;
         if ((rc = vec(l.x, l, true)) || (rc = vec(l.b, l, true)) || (rc = vec(l.r, l, true)) || (rc = vec(l.tmp, l, tmp)) ||
             (rc = vec(l.x32, l, f32)) || (rc = vec(l.b32, l, f32)) || (rc = vec(l.r32, l, f32)) || (rc = vec(l.tmp32, l, f32 && tmp))) return rc;
+    }
+    {   // the side vector of the folded head (fold_eligible asks for it): the first colour's slices, d columns
+        Level& l0 = h->lv[0];
+        const int fc = h->cfg.fold_head && !l0.ord.blocked ? first_color(l0) : -1;
+        l0.xh.reset(); l0.xh_rows = 0;
+        if (fc >= 0) {
+            const int rows = (l0.ord.color_begin[fc + 1] / 64 - l0.ord.color_begin[fc] / 64) * 64;
+            int rc = dev_alloc(h, l0.xh, (size_t)rows * d);
+            if (rc) return rc;
+            l0.xh_rows = rows;
+        }
     }
     Level& c = h->lv[h->L];
     size_t need = (size_t)c.n_pad * d * 2;
@@ -758,7 +813,7 @@ bool restrict_into(gmg_handle h, int k, int d, bool il) {
 // the way down from level k0.  first_done: the caller's restriction into level k0 ran that level's first pre-sweep (restrict_into's return
 // value: a caller that starts below level 0 restricted into level k0 itself); head_done: level 0's first colour launch is in the stream
 template <class T = double>
-void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, bool head_done = false) {
+void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, int head_done = 0) {
     const int L = h->L;
     for (int k = k0; k < L; ++k) {
         Level& l = h->lv[k];
@@ -766,7 +821,7 @@ void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, bool
         SmoothAsk<T> ask;
         ask.from_zero = k > 0 && smooth_from_zero_ok(h, l, h->cfg.pre_iters);      // eps.setZero (:1072-1073) folded into the first sweep
         if (k > 0 && !ask.from_zero) (void)hipMemsetAsync(Prec<T>::x(l), 0, sizeof(T) * (size_t)l.n_pad * d, h->stream);
-        ask.first_done = first_done; ask.head_done = k == 0 && head_done;
+        ask.first_done = first_done; ask.head_done = k == 0 ? head_done : 0;
         // d = 2 .. 4: the level-0 residual is written as an INTERLEAVED multi-vector (n x d row-major) -- only the restriction reads it, and a
         // gathered child then costs one cache line instead of d
         const bool il = k == 0 && d > 1 && d <= 4 && l.Aoff.lpr == 1;
@@ -1042,7 +1097,7 @@ int run_graph(gmg_handle h, int key, F&& enqueue) {
 // What the loop around the cycle knows -- head_done: this cycle's first colour launch is already in the stream (enqueue_head: never under a
 // graph); decide: the check's reduction also takes the loop's decision (CycleWatch; not the mixed-precision check: no head is eligible there).
 template <class T>
-int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, bool head_done, const CycleWatch* decide) {
+int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done, const CycleWatch* decide) {
     int rc;
     const int nt = norm_type < 0 ? 9 : norm_type;
     constexpr bool mixed = sizeof(T) == 4;
@@ -1079,7 +1134,7 @@ int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, bool head_done
     return rc ? rc : (served ? served : err);
 }
 
-int vcycle_resident(gmg_handle h, int d, int norm_type, bool head_done = false, const CycleWatch* decide = nullptr) {
+int vcycle_resident(gmg_handle h, int d, int norm_type, int head_done = 0, const CycleWatch* decide = nullptr) {
     if (h->cfg.inner_precision) return vcycle_legs<float>(h, d, norm_type, 100000, head_done, decide);
     return vcycle_legs<double>(h, d, norm_type, 0, head_done, decide);
 }

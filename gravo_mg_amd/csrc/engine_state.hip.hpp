@@ -156,6 +156,10 @@ struct Level {
     DevBuf<int> d_blk_of_row;         // refill the value arrays in place (refresh_system_values)
     DevBuf<double> x, b, r, tmp;      // n_pad * dcap (x, b, r of level 0: the caller's while gmg_dist_bind has them bound, DevBuf::borrow)
     DevBuf<float> diag32, x32, b32, r32, tmp32;      // mixed precision
+    // level 0, gmg_config::fold_head: the next cycle's first colour update as the residual check computed it (xh_rows = 64 * slices of the
+    // first colour per column, dcap columns, column-major; engine_cycle.hip.hpp::fold_eligible)
+    DevBuf<double> xh;
+    int xh_rows = 0;
 };
 
 }  // namespace
@@ -258,6 +262,8 @@ struct gmg_solver_s {
     // host has seen the norm, and returns at once when the iteration stopped.  Only the device words live here: what the reduction needs to
     // decide, and whether a head is in the stream, are the loop's locals and reach the launches as arguments (engine_cycle.hip.hpp: CycleWatch,
     // vcycle_resident) -- like everything else one launch of a cycle hands to another (SmoothAsk / SmoothDone): the handle keeps no such state.
+    // (gmg_config::fold_head: the check also computes that launch's values into Level::xh of level 0 and the launch enqueued ahead of the decision
+    // is the second colour launch, which commits them -- engine_cycle.hip.hpp::fold_eligible.)
     DevBuf<double> d_watch;
     double* h_pinned = nullptr; size_t pinned_cap = 0;     // coarse rhs / solution staging
     double* h_norm = nullptr;

@@ -49,9 +49,21 @@ template <int D, int XI> __device__ __forceinline__ int64_t x_at(int c, int d, i
 __device__ __forceinline__ float fma_of(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ double fma_of(double a, double b, double c) { return __builtin_fma(a, b, c); }
 
-template <class T, int D, int W, int XI = 0>
+// ALT (the folded head, gs_color_commit): the gathers of the columns [lo, lo + n) go to a side vector -- `shifted` is that vector's base minus lo,
+// so both sources are indexed by the column itself; its leading dimension is n.  One unsigned compare and a select (two at D > 1: the
+// stride) per gathered entry; without ALT nothing of this exists in the code.
+template <class T> struct AltRows { const T* shifted = nullptr; unsigned lo = 0, n = 0; };
+template <class T, int D>
+__device__ __forceinline__ T alt_at(const AltRows<T>& alt, const T* x, int c, int d, int ld) {
+    const bool in = (unsigned)c - alt.lo < alt.n;
+    const T* p = in ? alt.shifted : x;
+    if (D == 1) return p[c];
+    return p[c + (int64_t)d * (in ? (int)alt.n : ld)];
+}
+
+template <class T, int D, int W, int XI = 0, bool ALT = false>
 __device__ __forceinline__ void row_dot_group(const int* __restrict__ cp, const T* __restrict__ vp, const T* x, int ld,
-                                              T (&acc)[D]) {
+                                              T (&acc)[D], const AltRows<T>& alt = AltRows<T>{}) {
     int c[W];
     T v[W];
 #pragma unroll
@@ -60,7 +72,7 @@ __device__ __forceinline__ void row_dot_group(const int* __restrict__ cp, const 
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
-        for (int d = 0; d < D; ++d) xv[j][d] = x[x_at<D, XI>(c[j], d, ld)];
+        for (int d = 0; d < D; ++d) xv[j][d] = ALT ? alt_at<T, D>(alt, x, c[j], d, ld) : x[x_at<D, XI>(c[j], d, ld)];
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
@@ -73,10 +85,10 @@ __device__ __forceinline__ void row_dot_group(const int* __restrict__ cp, const 
 // (G entries per group: 8 with one or two right-hand sides; 6 with three -- a mesh row's six entries are one group, 90 VGPRs, 5 wavefronts
 // per SIMD: 22.9 us per colour launch against 23.5 with groups of 4 and 8 wavefronts --; 4 with four)
 template <int D> struct DotGroup { static constexpr int value = D >= 4 ? 4 : (D == 3 ? 6 : 8); };
-template <class T, int D, int G = DotGroup<D>::value, int XI = 0>
+template <class T, int D, int G = DotGroup<D>::value, int XI = 0, bool ALT = false>
 __device__ __forceinline__ void row_dot(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
                                         const T* __restrict__ val, const T* x, int ld, int s, int lane,
-                                        T (&acc)[D], int uw = 0) {
+                                        T (&acc)[D], int uw = 0, const AltRows<T>& alt = AltRows<T>{}) {
     // uw > 0: every slice of this operator is uw entries wide (DevSell::uniform_w) -- the slice's place follows from its number and the wave's
     // first loads are the entries themselves, not the two pointers they would otherwise wait for (one dependent memory round trip less per wave)
     const int64_t p0 = uw ? (int64_t)s * (uw << 6) : slice_ptr[s];
@@ -85,15 +97,15 @@ __device__ __forceinline__ void row_dot(const int64_t* __restrict__ slice_ptr, c
     const T* vp = val + p0 + lane;
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] = 0.0;
-    for (; w >= G; w -= G, cp += G * 64, vp += G * 64) row_dot_group<T, D, G, XI>(cp, vp, x, ld, acc);
+    for (; w >= G; w -= G, cp += G * 64, vp += G * 64) row_dot_group<T, D, G, XI, ALT>(cp, vp, x, ld, acc, alt);
     switch (w) {                                                   // w < G here
-        case 1: row_dot_group<T, D, 1, XI>(cp, vp, x, ld, acc); break;
-        case 2: row_dot_group<T, D, 2, XI>(cp, vp, x, ld, acc); break;
-        case 3: row_dot_group<T, D, 3, XI>(cp, vp, x, ld, acc); break;
-        case 4: if (G > 4) row_dot_group<T, D, 4, XI>(cp, vp, x, ld, acc); break;
-        case 5: if (G > 4) row_dot_group<T, D, 5, XI>(cp, vp, x, ld, acc); break;
-        case 6: if (G > 4) row_dot_group<T, D, 6, XI>(cp, vp, x, ld, acc); break;
-        case 7: if (G > 4) row_dot_group<T, D, 7, XI>(cp, vp, x, ld, acc); break;
+        case 1: row_dot_group<T, D, 1, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 2: row_dot_group<T, D, 2, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 3: row_dot_group<T, D, 3, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 4: if (G > 4) row_dot_group<T, D, 4, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 5: if (G > 4) row_dot_group<T, D, 5, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 6: if (G > 4) row_dot_group<T, D, 6, XI, ALT>(cp, vp, x, ld, acc, alt); break;
+        case 7: if (G > 4) row_dot_group<T, D, 7, XI, ALT>(cp, vp, x, ld, acc, alt); break;
         default: break;
     }
 }
@@ -108,9 +120,9 @@ __device__ __forceinline__ void row_dot(const int64_t* __restrict__ slice_ptr, c
 // order: the results are bit-identical to the 32-bit path.  A slice that NW windows cannot cover (rows of tiny colour classes,
 // scattered over the mesh) carries -1 as its first base and is read through the 32-bit indices: the wave learns that from the base
 // register AFTER it has issued its first group of loads, so the other slices never wait for the answer.
-template <class T, int D, int W, bool FLAGS, int XI = 0, bool KEEP = false>
+template <class T, int D, int W, bool FLAGS, int XI = 0, bool KEEP = false, bool ALT = false>
 __device__ __forceinline__ void row_dot_group16(const unsigned* __restrict__ cp, const int* __restrict__ cp32, const T* __restrict__ vp, const T* x, int ld,
-                                                int basev, int dbits, int& fallback, T (&acc)[D]) {
+                                                int basev, int dbits, int& fallback, T (&acc)[D], const AltRows<T>& alt = AltRows<T>{}) {
     unsigned pk[(W + 1) / 2];
     T v[W];
     // KEEP: the level's operators are small enough to stay on the chip between the launches that read them (DevSell::resident) -- ordinary
@@ -136,7 +148,7 @@ __device__ __forceinline__ void row_dot_group16(const unsigned* __restrict__ cp,
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
-        for (int d = 0; d < D; ++d) xv[j][d] = x[x_at<D, XI>(c[j], d, ld)];
+        for (int d = 0; d < D; ++d) xv[j][d] = ALT ? alt_at<T, D>(alt, x, c[j], d, ld) : x[x_at<D, XI>(c[j], d, ld)];
 #pragma unroll
     for (int j = 0; j < W; ++j)
 #pragma unroll
@@ -144,9 +156,10 @@ __device__ __forceinline__ void row_dot_group16(const unsigned* __restrict__ cp,
 }
 
 // row_dot with the columns read from the codes (G is even: a group's codes are whole words)
-template <class T, int D, bool FLAGS, int G = DotGroup<D>::value, int XI = 0, bool KEEP = false>
+template <class T, int D, bool FLAGS, int G = DotGroup<D>::value, int XI = 0, bool KEEP = false, bool ALT = false>
 __device__ __forceinline__ void row_dot16(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col, const unsigned* __restrict__ col16,
-                                          const int* __restrict__ win_base, int dbits, const T* __restrict__ val, const T* x, int ld, int s, int lane, T (&acc)[D], int uw = 0) {
+                                          const int* __restrict__ win_base, int dbits, const T* __restrict__ val, const T* x, int ld, int s, int lane, T (&acc)[D], int uw = 0,
+                                          const AltRows<T>& alt = AltRows<T>{}) {
     const int wshift = 16 - dbits;                                        // windows per slice = 1 << wshift
     const int basev = win_base[((int64_t)s << wshift) + (lane & ((1 << wshift) - 1))];
     const int64_t p0 = uw ? (int64_t)s * (uw << 6) : slice_ptr[s];        // (uw: see row_dot)
@@ -157,15 +170,15 @@ __device__ __forceinline__ void row_dot16(const int64_t* __restrict__ slice_ptr,
     int fallback = -1;                                                    // not known yet
 #pragma unroll
     for (int c = 0; c < D; ++c) acc[c] = 0.0;
-    for (; w >= G; w -= G, cp += (G / 2) * 64, cp32 += G * 64, vp += G * 64) row_dot_group16<T, D, G, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc);
+    for (; w >= G; w -= G, cp += (G / 2) * 64, cp32 += G * 64, vp += G * 64) row_dot_group16<T, D, G, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt);
     switch (w) {
-        case 1: row_dot_group16<T, D, 1, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 2: row_dot_group16<T, D, 2, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 3: row_dot_group16<T, D, 3, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 4: if (G > 4) row_dot_group16<T, D, 4, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 5: if (G > 4) row_dot_group16<T, D, 5, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 6: if (G > 4) row_dot_group16<T, D, 6, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
-        case 7: if (G > 4) row_dot_group16<T, D, 7, FLAGS, XI, KEEP>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc); break;
+        case 1: row_dot_group16<T, D, 1, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 2: row_dot_group16<T, D, 2, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 3: row_dot_group16<T, D, 3, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 4: if (G > 4) row_dot_group16<T, D, 4, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 5: if (G > 4) row_dot_group16<T, D, 5, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 6: if (G > 4) row_dot_group16<T, D, 6, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
+        case 7: if (G > 4) row_dot_group16<T, D, 7, FLAGS, XI, KEEP, ALT>(cp, cp32, vp, x, ld, basev, dbits, fallback, acc, alt); break;
         default: break;
     }
 }
@@ -175,18 +188,18 @@ __device__ __forceinline__ void row_dot16(const int64_t* __restrict__ slice_ptr,
 // classes come first -- and the branch on the wave-uniform slice number has nothing to wait for).  C16 = 2: uncovered slices anywhere,
 // found through their flag.  c16_arg = from (24 bits) | uniform slice width << 24 (6 bits, 0: widths differ -- read the slice pointers) | format << 30
 // (format 0: 13 offset bits / 8 windows, 1: 11 offset bits / 32 windows).
-template <class T, int D, int C16, int G = DotGroup<D>::value, int XI = 0>
+template <class T, int D, int C16, int G = DotGroup<D>::value, int XI = 0, bool ALT = false>
 __device__ __forceinline__ void row_dot_sel(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col, const unsigned* __restrict__ col16,
                                             const int* __restrict__ win_base, int c16_arg, const T* __restrict__ val, const T* x, int ld, int s, int lane,
-                                            T (&acc)[D]) {
+                                            T (&acc)[D], const AltRows<T>& alt = AltRows<T>{}) {
     if constexpr (C16 == 1 || C16 == 3) {
         const int dbits = (c16_arg >> 30) & 1 ? 11 : 13;
         const int uw = (c16_arg >> 24) & 63;
-        if (s >= (c16_arg & 0xffffff)) row_dot16<T, D, false, G, XI, C16 == 3>(slice_ptr, col, col16, win_base, dbits, val, x, ld, s, lane, acc, uw);
-        else row_dot<T, D, G, XI>(slice_ptr, col, val, x, ld, s, lane, acc, uw);
+        if (s >= (c16_arg & 0xffffff)) row_dot16<T, D, false, G, XI, C16 == 3, ALT>(slice_ptr, col, col16, win_base, dbits, val, x, ld, s, lane, acc, uw, alt);
+        else row_dot<T, D, G, XI, ALT>(slice_ptr, col, val, x, ld, s, lane, acc, uw, alt);
     } else if constexpr (C16 == 2 || C16 == 4) {
-        row_dot16<T, D, true, G, XI, C16 == 4>(slice_ptr, col, col16, win_base, (c16_arg >> 30) & 1 ? 11 : 13, val, x, ld, s, lane, acc, (c16_arg >> 24) & 63);
-    } else row_dot<T, D, G, XI>(slice_ptr, col, val, x, ld, s, lane, acc);
+        row_dot16<T, D, true, G, XI, C16 == 4, ALT>(slice_ptr, col, col16, win_base, (c16_arg >> 30) & 1 ? 11 : 13, val, x, ld, s, lane, acc, (c16_arg >> 24) & 63, alt);
+    } else row_dot<T, D, G, XI, ALT>(slice_ptr, col, val, x, ld, s, lane, acc, 0, alt);
 }
 
 // Quad layout (LPR = 4 lanes per row): add the four sub-lane partial sums; every lane of the quad gets the total.
@@ -270,6 +283,53 @@ __global__ __launch_bounds__(kBlock) void gs_color(const int64_t* __restrict__ s
 #pragma unroll
         for (int c = 0; c < D; ++c) {
             const T xi = x[row + (int64_t)c * ld];
+            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
+        }
+    }
+}
+
+// The SECOND colour launch of a cycle whose first colour update came out of the residual check in front of it (residual_norm_slices_head:
+// `xh` holds x_new of the rows [hb*64, he*64), column-major with leading dimension (he - hb)*64; x still holds the checked iterate there).
+// Blocks [0, n_work): gs_color's update of the slices [slice_begin, slice_end), the gathers of first-colour columns taken from xh (AltRows).
+// Blocks [n_work, gridDim): the commit, x <- xh on the first colour's rows, two rows per lane.  Nothing in this launch reads x at those rows
+// (rows of a colour do not couple to their own colour, and every other gather of them goes to xh), so the copy races with nothing and no
+// workgroup waits for another; later launches read x as before.  `go`: as in gs_color -- this launch is the one enqueued ahead of the loop's
+// decision, and a stopped iteration leaves x the iterate that was checked.  (A kernel of its own, not a flag of gs_color: the arguments a flag
+// would add are part of every instantiation's mangled name.)
+template <int D, int C16>
+__global__ __launch_bounds__(kBlock) void gs_color_commit(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
+                                                          const double* __restrict__ val, const double* __restrict__ diag,
+                                                          const double* __restrict__ b, double* x, int ld, int slice_begin, int slice_end,
+                                                          int n_work, double omega, const unsigned* __restrict__ col16, const int* __restrict__ win_base,
+                                                          int c16_arg, const double* __restrict__ xh, int hb, int he, const int* __restrict__ go) {
+    if (*go == 0) return;
+    const int lane = threadIdx.x & 63;
+    const int hrows = (he - hb) * 64;
+    if ((int)blockIdx.x >= n_work) {
+        const int r = (((int)blockIdx.x - n_work) * kBlock + (int)threadIdx.x) * 2;      // (hrows is a multiple of 64: a pair is inside or outside)
+        if (r >= hrows) return;
+#pragma unroll
+        for (int c = 0; c < D; ++c)
+            *reinterpret_cast<double2*>(x + (int64_t)hb * 64 + r + (int64_t)c * ld) = *reinterpret_cast<const double2*>(xh + r + (int64_t)c * hrows);
+        return;
+    }
+    int bb = blockIdx.x;
+    if ((n_work & 7) == 0) bb = (bb & 7) * (n_work >> 3) + (bb >> 3);                      // wave_slice's XCD map over the working blocks
+    const int s = slice_begin + __builtin_amdgcn_readfirstlane(bb * kWavesPerBlock + (int)(threadIdx.x >> 6));
+    if (s >= slice_end) return;
+    const int row = s * 64 + lane;
+    AltRows<double> alt;
+    alt.shifted = xh - (int64_t)hb * 64; alt.lo = (unsigned)hb * 64u; alt.n = (unsigned)hrows;
+    double acc[D];
+    row_dot_sel<double, D, C16, DotGroup<D>::value, 0, true>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc, alt);
+    const double dg = diag[row];
+    if (omega == 1.0) {
+#pragma unroll
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg);
+    } else {
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            const double xi = x[row + (int64_t)c * ld];
             x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
         }
     }
@@ -1742,6 +1802,47 @@ __global__ __launch_bounds__(kNormWaves * 64, 8) void residual_norm_slices(const
             else r = row_ax(acc[c], dg, x[row + (int64_t)c * ld]) - bi;
             sums[2 * c] = norm_term(r, w);
             sums[2 * c + 1] = norm_term(bi, w);
+        }
+    }
+    block_sums_store<kNormWaves, D>(sums, red, wave, lane, bb, partials);
+}
+
+// residual_norm_slices<D, 0, C16> that also produces the NEXT cycle's first colour update: nothing changes x between this check and that
+// launch, so for the slices [hb, he) of the first colour the off-diagonal sum, the diagonal, b_i and x_i it would load are in registers here.
+// Those slices apply the launch's own functions to them (gs_row, the plain form at omega = 1) and store the result to the side vector xh
+// ((he - hb)*64 rows per column, column-major); x is not written, and the kernel does not depend on the loop's decision: no `go` word.  The
+// sums are those of residual_norm_slices, term for term.  gs_color_commit consumes xh.
+template <int D, int C16>
+__global__ __launch_bounds__(kNormWaves * 64, 8) void residual_norm_slices_head(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
+                                                               const double* __restrict__ val, const double* __restrict__ diag,
+                                                               const double* __restrict__ b, const double* __restrict__ x,
+                                                               const double* __restrict__ weight, int ld, int n_slices, double* __restrict__ partials,
+                                                               const unsigned* __restrict__ col16, const int* __restrict__ win_base, int c16_arg,
+                                                               double* __restrict__ xh, int hb, int he, double omega) {
+    __shared__ double red[kNormWaves][2 * D];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int nblk = gridDim.x, bb = blockIdx.x;
+    if ((nblk & 7) == 0) bb = (bb & 7) * (nblk >> 3) + (bb >> 3);
+    const int s = __builtin_amdgcn_readfirstlane(bb * kNormWaves + wave);
+    double sums[2 * D];
+#pragma unroll
+    for (int c = 0; c < 2 * D; ++c) sums[c] = 0.0;
+    if (s < n_slices) {
+        const int row = s * 64 + lane;
+        double acc[D];
+        row_dot_sel<double, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
+        const double dg = diag[row];
+        const double w = weight ? weight[row] : 1.0;
+        const bool head = s >= hb && s < he;                               // wave-uniform
+        const int64_t hrows = (int64_t)(he - hb) * 64;
+#pragma unroll
+        for (int c = 0; c < D; ++c) {
+            const double bi = b[row + (int64_t)c * ld];
+            const double xi = x[row + (int64_t)c * ld];
+            const double r = row_ax(acc[c], dg, xi) - bi;
+            sums[2 * c] = norm_term(r, w);
+            sums[2 * c + 1] = norm_term(bi, w);
+            if (head) xh[(row - hb * 64) + c * hrows] = omega == 1.0 ? gs_row(bi, acc[c], dg) : gs_row(bi, acc[c], dg, omega, xi);
         }
     }
     block_sums_store<kNormWaves, D>(sums, red, wave, lane, bb, partials);

@@ -152,6 +152,15 @@ typedef struct {
     int color_ahead;       /* 1 (default): a gmg_set_system that cannot be a values-only refresh starts the greedy colouring of level 0 (one core, 10-13 ms at
                               3 M vertices: the longest task of a cold set-up) at entry, beside the inspection of the caller's arrays, with every index checked;
                               the result is used when the inspection and the layout decisions allow it -- the same colours, ~6 ms earlier.  0: after them */
+    int fold_head;         /* 1 (default): where speculate_head enqueues a head, the residual check in front of it also computes the first colour update of the
+                              next cycle -- it has read those rows and holds every operand -- and stores it to a side vector; the launch enqueued ahead of
+                              the decision is then the SECOND colour launch, which takes the first colour's values from the side vector and copies them into
+                              x.  One launch and one pass over the first colour's rows less per cycle; the same arithmetic on the same operands, so iterates,
+                              residues and iteration counts are unchanged bit for bit, and a stopped iteration leaves x the iterate that was checked.  Needs
+                              what speculate_head needs, pre_iters >= 1 and a second colour class on level 0 whose first launch is not the pre-smoothing's
+                              last; otherwise, and with 0, the head is the first colour launch.  Timing key "heads_folded" counts the folded heads
+                              ("heads_enqueued" counts every launch enqueued ahead of the decision, folded or not).  Added after accelerate, in front of which
+                              it stands: accelerate stays the last field, and a binding built against another edition is refused by gmg_config_size */
     int accelerate;        /* 0 (default): the solve loop as in the reference (cycle, residual check, repeat).  m in 1..4: gmg_solve, gmg_solve_x0_rhs and
                               gmg_solve_device recombine the iterates by truncated GCR with the V-cycle as the preconditioner: every cycle's step is
                               orthogonalised (in the stop type's weighted inner product, per right-hand-side column) against the last m - 1 stored
