@@ -162,6 +162,7 @@ INTERNAL_SIGNATURES = {
                                       C.POINTER(C.c_ubyte)]),
     "gmg_host_fine_block_rule": (C.c_int, [C.c_int, _ip, _ip, _dp, _ip, _ip]),
     "gmg_debug_set": (C.c_int, [_vp, C.c_char_p, C.c_double]),
+    "gmg_debug_f32_op": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gmg_bench_kernel": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip]),
     "gmg_profile_cycle": (C.c_int, [_vp, C.c_int, C.c_int, _dp, C.c_int]),
     "gmg_algorithmic_bytes": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, _dp]),
@@ -590,6 +591,54 @@ class Engine:
         out = C.c_double()
         self._chk(lib().gmg_residual_norm(self._h, _pd(B), _pd(X), B.shape[1], int(type), C.byref(out)))
         return out.value
+
+    # -- the fp32 inner cycle's operators (inner_precision = 1), one at a time: gmg_debug_f32_op.  Arguments and results are float64 arrays; what
+    # the device computes on is their rounding to float32 (pass fp32-representable values and the conversions are exact)
+    F32_SMOOTH, F32_SMOOTH_RESIDUAL, F32_RESIDUAL, F32_SPMV, F32_RESTRICT, F32_RESTRICT_SWEEPS, F32_PROLONG_ADD, F32_COARSE, F32_DEFECT, F32_CORRECT = range(10)
+
+    def _f32_op(self, op, k, in0, in1=None, iters=0, flag=0, out_rows=None, n_out=1):
+        A = _f64(in0)
+        B = None if in1 is None else _f64(in1)
+        d = A.shape[1]
+        outs = [np.empty((A.shape[0] if r is None else r, d), order="F") for r in (out_rows or [None] * n_out)]
+        ptr = [_pd(o) for o in outs] + [None] * (3 - len(outs))
+        self._chk(lib().gmg_debug_f32_op(self._h, int(op), int(k), d, int(iters), int(flag), _pd(A), None if B is None else _pd(B), *ptr))
+        return [self._shape_like(o, in0) for o in outs]
+
+    def smooth_f32(self, k, b, x, iters):
+        return self._f32_op(self.F32_SMOOTH, k, b, x, iters=iters)[0]
+
+    def smooth_residual_f32(self, k, b, x, iters, from_zero=False):
+        """(x after `iters` sweeps, b - A x as the fp32 way down forms it); timing("residual_from_sweep") says where the residual came from"""
+        return tuple(self._f32_op(self.F32_SMOOTH_RESIDUAL, k, b, None if from_zero else x, iters=iters, flag=int(bool(from_zero)), n_out=2))
+
+    def residual_f32(self, k, b, x):
+        return self._f32_op(self.F32_RESIDUAL, k, b, x)[0]
+
+    def spmv_f32(self, k, x):
+        return self._f32_op(self.F32_SPMV, k, x)[0]
+
+    def restrict_f32(self, k, r):
+        return self._f32_op(self.F32_RESTRICT, k, r, out_rows=[self._level_n(k + 1)])[0]
+
+    def restrict_sweeps_f32(self, k, r, iters):
+        """(U_k^T r, level k + 1's iterate after `iters` pre-sweeps from zero, its residual): the way down between levels k and k + 1"""
+        return tuple(self._f32_op(self.F32_RESTRICT_SWEEPS, k, r, iters=iters, out_rows=[self._level_n(k + 1)] * 3))
+
+    def prolong_add_f32(self, k, e, x):
+        return self._f32_op(self.F32_PROLONG_ADD, k, e, x, out_rows=[self._level_n(k)])[0]
+
+    def coarse_solve_f32(self, rc):
+        return self._f32_op(self.F32_COARSE, 0, rc)[0]
+
+    def defect_f32(self, b, x, type=2):
+        """(float32(b - A x) of the fp64 level 0, widened; the residual norm of that type)"""
+        B = _f64(b)
+        out, nrm = self._f32_op(self.F32_DEFECT, 0, b, x, flag=type, out_rows=[B.shape[0], 1])
+        return out, float(np.asarray(nrm).ravel()[0])
+
+    def correct_f32(self, e, x):
+        return self._f32_op(self.F32_CORRECT, 0, e, x)[0]
 
     # -- hot path
     def vcycle(self, b, x):

@@ -569,6 +569,122 @@ int gmg_residual_norm(gmg_handle h, const double* b, const double* x, int d, int
     return GMG_OK;
 } GMG_CATCH_H
 
+// ---- the fp32 inner cycle's operators, one at a time (include/gravomg_hip_internal.h) ------------------------------------------
+
+namespace {
+// host fp64 -> the level's fp64 vector -> its fp32 twin, and back (exact for fp32-representable values)
+int f32_in(gmg_handle h, int k, const double* src, int d, double* v64, float* v32) {
+    if (const int rc = to_device(h, k, src, d, v64)) return rc;
+    launch_cvt(h, v64, v32, (size_t)h->lv[k].n_pad * d);
+    return GMG_OK;
+}
+int f32_out(gmg_handle h, int k, const float* v32, double* v64, int d, double* dst) {
+    launch_cvt(h, v32, v64, (size_t)h->lv[k].n_pad * d);
+    return to_host(h, k, v64, d, dst);
+}
+// level l's smoothing from zero or from x32 as enqueue_down enqueues it, and the residual behind it; sets residual_from_sweep
+void f32_smooth_residual(gmg_handle h, int k, int d, int iters, bool from_zero, bool first_done) {
+    Level& l = h->lv[k];
+    SmoothAsk<float> ask;
+    ask.from_zero = from_zero && k > 0 && smooth_from_zero_ok(h, l, iters);
+    ask.first_done = first_done;
+    if (from_zero && !ask.from_zero) (void)hipMemsetAsync(l.x32, 0, sizeof(float) * (size_t)l.n_pad * d, h->stream);
+    const SmoothDone<float> swept = launch_smooth<float>(h, l, d, iters, ask);
+    const bool delta = k > 0 && launch_residual_delta<float>(h, l, d, l.r32, swept);
+    if (!delta) launch_spmv<float>(h, l, d, 1, l.b32, l.x32, l.r32);
+    h->timing["residual_from_sweep"] = delta ? 1.0 : 0.0;
+}
+}  // namespace
+
+int gmg_debug_f32_op(gmg_handle h, int op, int k, int d, int iters, int flag, const double* in0, const double* in1, double* out0, double* out1,
+                     double* out2) try {
+    NEED_DEVICE();
+    if (!h->cfg.inner_precision) return fail(h, GMG_ERR_STATE, "gmg_debug_f32_op needs a handle created with inner_precision = 1");
+    const bool coarse_op = op == GMG_F32_COARSE;
+    int rc = check_level(h, coarse_op ? h->L : k, coarse_op);
+    if (rc) return rc;
+    if ((rc = check_whole_system(h))) return rc;
+    if (!in0 || !out0 || d <= 0 || iters < 0) return fail(h, GMG_ERR_INVALID, "bad arguments");
+    if ((rc = ensure_vectors(h, d))) return rc;
+    h->loaded_d = 0;
+    if (coarse_op) {
+        Level& c = h->lv[h->L];
+        if ((rc = f32_in(h, h->L, in0, d, c.b, c.b32))) return rc;
+        if (h->coarse_device) enqueue_coarse_device<float>(h, d);
+        else if ((rc = coarse_host_roundtrip<float>(h, d))) return rc;
+        return f32_out(h, h->L, c.x32, c.x, d, out0);
+    }
+    Level& l = h->lv[k];
+    Level& c = h->lv[k + 1];
+    switch (op) {
+    case GMG_F32_SMOOTH:                      // in0 b, in1 x -> out0 x
+        if (!in1) break;
+        if ((rc = f32_in(h, k, in0, d, l.b, l.b32)) || (rc = f32_in(h, k, in1, d, l.x, l.x32))) return rc;
+        launch_smooth<float>(h, l, d, iters);
+        return f32_out(h, k, l.x32, l.x, d, out0);
+    case GMG_F32_SMOOTH_RESIDUAL:             // in0 b, in1 x (flag = from_zero: not read) -> out0 x, out1 r
+        if (!out1 || (!flag && !in1)) break;
+        if ((rc = f32_in(h, k, in0, d, l.b, l.b32))) return rc;
+        if (!flag && (rc = f32_in(h, k, in1, d, l.x, l.x32))) return rc;
+        f32_smooth_residual(h, k, d, iters, flag != 0, false);
+        if ((rc = f32_out(h, k, l.x32, l.x, d, out0))) return rc;
+        return f32_out(h, k, l.r32, l.r, d, out1);
+    case GMG_F32_RESIDUAL:                    // in0 b, in1 x -> out0 b - A x
+        if (!in1) break;
+        if ((rc = f32_in(h, k, in0, d, l.b, l.b32)) || (rc = f32_in(h, k, in1, d, l.x, l.x32))) return rc;
+        launch_spmv<float>(h, l, d, 1, l.b32, l.x32, l.r32);
+        return f32_out(h, k, l.r32, l.r, d, out0);
+    case GMG_F32_SPMV:                        // in0 x -> out0 A x
+        if ((rc = f32_in(h, k, in0, d, l.x, l.x32))) return rc;
+        launch_spmv<float>(h, l, d, 0, nullptr, l.x32, l.r32);
+        return f32_out(h, k, l.r32, l.r, d, out0);
+    case GMG_F32_RESTRICT:                    // in0 r_k -> out0 b_{k+1}
+        if ((rc = f32_in(h, k, in0, d, l.r, l.r32))) return rc;
+        launch_restrict<float>(h, l, c, d, l.r32, c.b32);
+        return f32_out(h, k + 1, c.b32, c.b, d, out0);
+    case GMG_F32_RESTRICT_SWEEPS: {           // in0 r_k -> out0 b_{k+1}, out1 x_{k+1} after `iters` pre-sweeps from zero, out2 its residual
+        if (!out1 || !out2 || iters <= 0) break;
+        if (k + 1 >= h->L) return fail(h, GMG_ERR_INVALID, "level k + 1 is the coarsest: it is not smoothed");
+        // (d = 2 .. 4 on level 0: the way down hands the restriction an interleaved residual, which the residual launch writes -- from x = 0 it is r_k itself)
+        const bool il = k == 0 && d > 1 && d <= 4 && l.Aoff.lpr == 1;
+        if (il) {
+            if ((rc = f32_in(h, k, in0, d, l.b, l.b32))) return rc;
+            (void)hipMemsetAsync(l.x32, 0, sizeof(float) * (size_t)l.n_pad * d, h->stream);
+            launch_spmv<float>(h, l, d, 1, l.b32, l.x32, l.r32, -1, true);
+        } else if ((rc = f32_in(h, k, in0, d, l.r, l.r32))) return rc;
+        struct PreIters { int& v; int old; ~PreIters() { v = old; } } keep{h->cfg.pre_iters, h->cfg.pre_iters};      // (restrict_into asks the configuration)
+        h->cfg.pre_iters = iters;
+        const bool first_done = restrict_into<float>(h, k, d, il);
+        f32_smooth_residual(h, k + 1, d, iters, true, first_done);
+        if ((rc = f32_out(h, k + 1, c.b32, c.b, d, out0)) || (rc = f32_out(h, k + 1, c.x32, c.x, d, out1))) return rc;
+        return f32_out(h, k + 1, c.r32, c.r, d, out2);
+    }
+    case GMG_F32_PROLONG_ADD:                 // in0 e_{k+1}, in1 x_k -> out0 x_k + U e
+        if (!in1) break;
+        if ((rc = f32_in(h, k + 1, in0, d, c.x, c.x32)) || (rc = f32_in(h, k, in1, d, l.x, l.x32))) return rc;
+        launch_prolong_add<float>(h, l, c, d, c.x32, l.x32);
+        return f32_out(h, k, l.x32, l.x, d, out0);
+    case GMG_F32_DEFECT: {                    // level 0: in0 b, in1 x (fp64) -> out0 b32 widened, out1[0] the norm of type `flag`
+        if (!in1 || !out1 || k != 0) break;
+        if ((rc = check_norm_type(h, flag))) return rc;
+        if ((rc = to_device(h, 0, in0, d, l.b)) || (rc = to_device(h, 0, in1, d, l.x))) return rc;
+        if ((rc = launch_residual_to_f32(h, d, flag)) || (rc = wait_norm(h))) return rc;
+        out1[0] = norm_from_sums(h->h_norm, d, flag);
+        return f32_out(h, 0, l.b32, l.r, d, out0);
+    }
+    case GMG_F32_CORRECT: {                   // level 0: in0 an fp32 vector, in1 x (fp64) -> out0 x + in0
+        if (!in1 || k != 0) break;
+        if ((rc = f32_in(h, 0, in0, d, l.r, l.x32)) || (rc = to_device(h, 0, in1, d, l.x))) return rc;
+        const size_t cnt = (size_t)l.n_pad * d;
+        hipLaunchKernelGGL(gmgk::add_correction, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, l.x32, l.x, (int64_t)cnt);
+        return to_host(h, 0, l.x, d, out0);
+    }
+    default:
+        return fail(h, GMG_ERR_INVALID, "unknown operation");
+    }
+    return fail(h, GMG_ERR_INVALID, "bad arguments");
+} GMG_CATCH_H
+
 // ---- resident problem: load / run / fetch ------------------------------------------------------------------
 
 int gmg_load_problem(gmg_handle h, const double* b, const double* x0, int d) try {

@@ -471,7 +471,7 @@ __global__ __launch_bounds__(kBlockRows) void gs_block(const int* __restrict__ b
         }
 #pragma unroll
         for (int c = 0; c < D; ++c) rhs[c] = b[row + (int64_t)c * ld] - acc[c];
-        dg = 1.0 / diag[row];      // reciprocal once, outside the sequential colour loop
+        dg = (T)1.0 / diag[row];      // reciprocal once, outside the sequential colour loop
         mycolor = row_color[row];
     }
     __syncthreads();
@@ -494,13 +494,13 @@ __global__ __launch_bounds__(kBlockRows) void gs_block(const int* __restrict__ b
 #pragma unroll
                     for (int j = 0; j < CH; ++j)
 #pragma unroll
-                        for (int c = 0; c < D; ++c) s_[c] += v[j0 + j] * xv[j][c];
+                        for (int c = 0; c < D; ++c) s_[c] = fma_of(v[j0 + j], xv[j][c], s_[c]);
                 }
             for (int j = WIN; j < w; ++j) {                 // rows longer than the register window (rare)
                 const T vj = in_val[p0 + (int64_t)j * 64 + lane];
                 const int cj = in_col[p0 + (int64_t)j * 64 + lane];
 #pragma unroll
-                for (int c = 0; c < D; ++c) s_[c] += vj * xs[c][cj];
+                for (int c = 0; c < D; ++c) s_[c] = fma_of(vj, xs[c][cj], s_[c]);
             }
 #pragma unroll
             for (int c = 0; c < D; ++c) xs[c][t] = (rhs[c] - s_[c]) * dg;
@@ -521,7 +521,10 @@ __global__ __launch_bounds__(kBlockRows) void gs_block(const int* __restrict__ b
 // ONE contiguous chunk, which the wave copies into LDS with perfectly coalesced loads; every lane then sums its row's
 // couplings from there (x gathered from the previous iterate).  The in-block operator stays in SELL (its entries go
 // to registers for the colour loop, exactly as in gs_block).  Same arithmetic, same order: results are bitwise those
-// of gs_block.
+// of gs_block -- which a single right-hand side runs where a block of them runs this kernel (launch_block_sweep_range), so one column
+// alone must give the bits of that column in a block.  Both kernels therefore accumulate with fma_of and form the reciprocal of the
+// diagonal in T: written as `s += v * x`, the compiler fused some instantiations and split others into a multiply and an add
+// (tests/test_gpu_mixed_operators.py found the float ones apart on a 480-entry row).
 template <class T, int D, int WIN>
 __global__ __launch_bounds__(64) void gs_block_csrout(const int* __restrict__ blk_begin, const int* __restrict__ blk_ncolors,
                                                       const unsigned char* __restrict__ row_color,
@@ -586,12 +589,12 @@ __global__ __launch_bounds__(64) void gs_block_csrout(const int* __restrict__ bl
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int c = 0; c < D; ++c) acc[c] += vv[j] * xv[j][c];
+                for (int c = 0; c < D; ++c) acc[c] = fma_of(vv[j], xv[j][c], acc[c]);
         }
         for (; e < me; ++e) {
             const int cj = scol[e]; const T vj = sval[e];
 #pragma unroll
-            for (int c = 0; c < D; ++c) acc[c] += vj * x_in[cj + (int64_t)c * ld];
+            for (int c = 0; c < D; ++c) acc[c] = fma_of(vj, x_in[cj + (int64_t)c * ld], acc[c]);
         }
 #pragma unroll
         for (int c = 0; c < D; ++c) rhs[c] = b[row + (int64_t)c * ld] - acc[c];
@@ -615,13 +618,13 @@ __global__ __launch_bounds__(64) void gs_block_csrout(const int* __restrict__ bl
 #pragma unroll
                     for (int j = 0; j < CH; ++j)
 #pragma unroll
-                        for (int c = 0; c < D; ++c) s_[c] += v[j0 + j] * xv[j][c];
+                        for (int c = 0; c < D; ++c) s_[c] = fma_of(v[j0 + j], xv[j][c], s_[c]);
                 }
             for (int j = WIN; j < w; ++j) {                            // rows longer than the register window (rare)
                 const T vj = in_val[p0 + (int64_t)j * 64 + lane];
                 const int cj = in_col[p0 + (int64_t)j * 64 + lane];
 #pragma unroll
-                for (int c = 0; c < D; ++c) s_[c] += vj * xs[c * 64 + cj];
+                for (int c = 0; c < D; ++c) s_[c] = fma_of(vj, xs[c * 64 + cj], s_[c]);
             }
 #pragma unroll
             for (int c = 0; c < D; ++c) xs[c * 64 + lane] = (rhs[c] - s_[c]) * dg;

@@ -46,6 +46,28 @@ int gmg_debug_select_parents(int nf, int nc, int Kc, int ntri, int weighting, in
  * single / one neighbour.  Lets an end-to-end test say which branches of the selection its input reached. */
 int gmg_hierarchy_debug_row_kinds(gmg_hierarchy hh, int k, int* out);
 
+/* One operator of the fp32 inner V-cycle (gmg_config::inner_precision = 1; GMG_ERR_STATE on any other handle) through the cycle's own launch
+ * code: host fp64 arrays (natural numbering, column-major n x d) go into the level's fp64 vectors, are converted to its fp32 vectors (exact for
+ * fp32-representable values), the launch_*<float> / enqueue_*<float> functions of the way down and the way up run, and the results are
+ * widened and copied back.  No kernel runs that a cycle does not run.  op (k = level; in1 / out1 / out2 may be NULL where not listed):
+ *   SMOOTH           in0 b, in1 x                 -> out0 x after `iters` sweeps of the handle's smoother
+ *   SMOOTH_RESIDUAL  in0 b, in1 x, flag from_zero -> out0 x, out1 b - A x as the way down forms it behind the sweeps (from_zero: in1 is not
+ *                                                    read; timing key residual_from_sweep = 1 where it came from the sweep's explicit part)
+ *   RESIDUAL / SPMV  in0 b, in1 x / in0 x         -> out0 b - A x / A x
+ *   RESTRICT         in0 r_k                      -> out0 U_k^T r_k (n_{k+1} rows)
+ *   RESTRICT_SWEEPS  in0 r_k, k + 1 < levels      -> out0 U_k^T r_k, out1 level k + 1's iterate after `iters` >= 1 pre-sweeps from zero, out2 its
+ *                                                    residual: what the way down does between two levels, fused into one launch where
+ *                                                    gmg_config::fuse_restrict_sweep engages (timing key restrict_sweeps_fused counts); on
+ *                                                    level 0 with d = 2 .. 4 the restriction reads the interleaved residual, as in a cycle
+ *   PROLONG_ADD      in0 e_{k+1}, in1 x_k         -> out0 x_k + U_k e
+ *   COARSE           in0 rc (k ignored)           -> out0 the fp64 coarsest solve of float(rc), rounded to fp32
+ *   DEFECT           k = 0, in0 b, in1 x (fp64), flag norm type 0..3 -> out0 float(b - A x) widened, out1[0] the norm of b - A x
+ *   CORRECT          k = 0, in0 e (fp32 values), in1 x (fp64)        -> out0 x + e, added in fp64 */
+enum { GMG_F32_SMOOTH = 0, GMG_F32_SMOOTH_RESIDUAL = 1, GMG_F32_RESIDUAL = 2, GMG_F32_SPMV = 3, GMG_F32_RESTRICT = 4, GMG_F32_RESTRICT_SWEEPS = 5,
+       GMG_F32_PROLONG_ADD = 6, GMG_F32_COARSE = 7, GMG_F32_DEFECT = 8, GMG_F32_CORRECT = 9 };
+int gmg_debug_f32_op(gmg_handle h, int op, int k, int d, int iters, int flag, const double* in0, const double* in1, double* out0, double* out1,
+                     double* out2);
+
 /* Host-only Galerkin product Ac = U^T A U (CSC in / CSC out, caller sizes the output with the first call:
  * pass colptr_out only to get nnz in colptr_out[n_coarse]).  Exposed for the RAP parity tests. */
 int gmg_host_galerkin(int n, const int* a_colptr, const int* a_rowidx, const double* a_val,
