@@ -158,6 +158,8 @@ INTERNAL_SIGNATURES = {
     "gmg_hierarchy_debug_row_kinds": (C.c_int, [_vp, C.c_int, _ip]),
     "gmg_host_galerkin": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, _ip, _ip, _dp, _ip, _ip, _dp]),
     "gmg_debug_device_galerkin": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, _dp, C.c_int, _ip, _ip, _dp, C.c_int64, _ip, _ip, _dp, _dp, _ip]),
+    "gmg_debug_coarse_inverse": (C.c_int, [_vp, C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, _dp, C.c_int64, C.POINTER(C.c_int64), _ip, _ip, _ip, _ip, _ip, _dp, _dp, _dp,
+                                           _ip, _ip, _ip, _ip, _ip]),
     "gmg_host_plan_level": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_ubyte)]),
     "gmg_host_fine_block_rule": (C.c_int, [C.c_int, _ip, _ip, _dp, _ip, _ip]),
@@ -912,6 +914,52 @@ def device_galerkin(eng: "Engine", A, U, val2=None):
         return status.value, None, None
     nnz = int(colptr[nc])
     return 0, sp.csc_matrix((val[:nnz].copy(), rowidx[:nnz].copy(), colptr), shape=(nc, nc)), (out2[:nnz].copy() if out2 is not None else None)
+
+
+COARSE_INVERSE_INFO = ("chunks", "levels", "tiles", "width", "big_chunks", "max_level_chunks", "max_rows", "max_small_rows", "narrow_chunks", "roots",
+                       "row_entries", "tile_entries", "out_doubles", "out_ld", "big_rows", "waves")
+
+
+def coarse_inverse(eng, A, width: int = 0, mode: int = 0, export: bool = False):
+    """The dense inverse of the SPD matrix A as the set-up's own code builds it (gmg_debug_coarse_inverse; the engine lends its stream and pool;
+    mode 0 runs on the host and takes eng = None).  A goes in AS STORED.  mode 0: the host's restatement of the kernel, lower triangle in the
+    factor's numbering; 1: the device's X in the factor's numbering, mirrored; 2 / 3: the full inverse in A's numbering through permute_symmetric /
+    permute_symmetric_scatter; 4: the packed triangle (flat).  Returns (matrix, info dict, exported factor as a dict of arrays or None)."""
+    a = _csc_layout(A)
+    n = a.shape[0]
+    h = eng._h if eng is not None else None
+    info = (C.c_int64 * 16)()
+    none = [None] * 13
+
+    def call(out, cap, arrays):
+        rc = lib().gmg_debug_coarse_inverse(h, n, _pi(a.indptr), _pi(a.indices), _pd(a.data), int(width), int(mode), out, cap, info, *arrays)
+        if rc:
+            raise GmgError(rc, lib().gmg_last_error(h).decode() if h else "gmg_debug_coarse_inverse")
+    call(None, 0, none)
+    inf = dict(zip(COARSE_INVERSE_INFO, (int(v) for v in info)))
+    E = None
+    arrays = none
+    if export:
+        nq, nlev, nt, nr = inf["chunks"], inf["levels"], inf["tiles"], inf["row_entries"]
+        i32 = lambda k: np.zeros(max(k, 1), np.int32)
+        f64 = lambda k: np.zeros(max(k, 1), np.float64)
+        E = dict(perm=i32(n), q_col0=i32(nq), q_w=i32(nq), q_rptr=i32(nq + 1), rows=i32(nr), vals=f64(8 * nr), tri=f64(64 * nq), dinv=f64(n),
+                 lev_ptr=i32(nlev + 1), lev_q=i32(nq), lev_big=i32(nlev), tile_ptr=i32(nt + 1), tile_q=i32(inf["tile_entries"]))
+        arrays = [(_pd if v.dtype == np.float64 else _pi)(v) for v in E.values()]
+    out = np.empty(inf["out_doubles"], np.float64)
+    call(_pd(out), out.size, arrays)
+    if E is not None:
+        nq, nlev, nt, nr = inf["chunks"], inf["levels"], inf["tiles"], inf["row_entries"]
+        sizes = dict(perm=n, q_col0=nq, q_w=nq, q_rptr=nq + 1, rows=nr, vals=8 * nr, tri=64 * nq, dinv=n, lev_ptr=nlev + 1, lev_q=nq, lev_big=nlev,
+                     tile_ptr=nt + 1, tile_q=inf["tile_entries"])
+        E = {k: v[:sizes[k]] for k, v in E.items()}
+        E["vals"] = E["vals"].reshape(nr, 8)
+        E["tri"] = E["tri"].reshape(nq, 8, 8)
+    if mode in (2, 3):
+        out = out.reshape(n, inf["out_ld"])[:, :n].copy()
+    elif mode != 4:
+        out = out.reshape(n, n)
+    return out, inf, E
 
 
 def host_galerkin(A, U, as_stored: bool = False) -> sp.csc_matrix:

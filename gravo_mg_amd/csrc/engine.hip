@@ -1640,6 +1640,68 @@ int gmg_debug_device_galerkin(gmg_handle h, int n, const int* a_colptr, const in
     return GMG_OK;
 } GMG_CATCH_H
 
+// Test access to the device-built coarse inverse (gravomg_hip_internal.h): the set-up's own factorisation, export and coarse_inverse_core on a
+// caller's matrix, into local DevBufs.  Of the handle only the stream, the pool, the bounce buffers and the scratch events are used.
+int gmg_debug_coarse_inverse(gmg_handle h, int n, const int* colptr, const int* rowidx, const double* val, int width, int mode, double* out, int64_t out_cap,
+                             int64_t* info, int* perm, int* q_col0, int* q_w, int* q_rptr, int* rows, double* vals, double* tri, double* dinv, int* lev_ptr,
+                             int* lev_q, int* lev_big, int* tile_ptr, int* tile_q) try {
+    if (n <= 0 || !colptr || !rowidx || !val || !info || mode < 0 || mode > 4 || (width != 0 && width != 16 && width != 32 && width != 64) || out_cap < 0)
+        return fail(h, GMG_ERR_INVALID, "bad arguments");
+    if (mode != 0) {
+        if (!h) return GMG_ERR_INVALID;
+        if (!h->has_device) return fail(h, GMG_ERR_NO_DEVICE, "no usable HIP device (libgravomg_hip has no CPU fallback)");
+    }
+    if (colptr[0] != 0) return fail(h, GMG_ERR_INVALID, "column pointers must start at 0");
+    for (int i = 0; i < n; ++i) if (colptr[i + 1] < colptr[i]) return fail(h, GMG_ERR_INVALID, "column pointers decrease");
+    for (int q = 0; q < colptr[n]; ++q) if (rowidx[q] < 0 || rowidx[q] >= n) return fail(h, GMG_ERR_INVALID, "row index out of range");
+    Compressed A;
+    A.assign(n, n, colptr, rowidx, val);
+    SupernodalLDLT f;
+    if (!f.factor(A)) return fail(h, GMG_ERR_NUMERIC, "the matrix is not positive definite");
+    SupernodalLDLT::DeviceFactor E;
+    f.export_device_factor(E);
+    const int w = width ? width : coarse_inverse_width(n);
+    std::vector<int> tile_ptr_h, tile_q_h;
+    E.tile_paths(w, tile_ptr_h, tile_q_h);
+    const std::vector<int> lev_big_h = E.big_per_level(gmgs::kInvBigRows);
+    const int lda = (n + 7) / 8 * 8, nb = tri_blocks(n);
+    long long shape[10];
+    E.shape_info(w, gmgs::kInvBigRows, shape);
+    for (int k = 0; k < 10; ++k) info[k] = shape[k];
+    info[10] = (int64_t)E.rows.size();
+    info[11] = (int64_t)tile_q_h.size();
+    info[12] = mode == 4 ? (int64_t)tri_block_count(nb) * kTriBlockDoubles : (mode == 2 || mode == 3) ? (int64_t)n * lda : (int64_t)n * n;
+    info[13] = (mode == 2 || mode == 3) ? lda : (mode == 4 ? 64 : n);
+    info[14] = gmgs::kInvBigRows;
+    info[15] = gmgs::kInvWaves;
+    auto give = [](auto* dst, const auto& src) { if (dst && !src.empty()) std::memcpy(dst, src.data(), sizeof(src[0]) * src.size()); };
+    give(perm, E.perm); give(q_col0, E.q_col0); give(q_w, E.q_w); give(q_rptr, E.q_rptr); give(rows, E.rows); give(vals, E.vals); give(tri, E.tri);
+    give(dinv, E.dinv); give(lev_ptr, E.lev_ptr); give(lev_q, E.lev_q); give(lev_big, lev_big_h); give(tile_ptr, tile_ptr_h); give(tile_q, tile_q_h);
+    if (!out) return GMG_OK;                                 // the sizing call
+    if (out_cap < info[12]) return fail(h, GMG_ERR_INVALID, "the output needs " + std::to_string(info[12]) + " doubles");
+    if (mode == 0) {
+        // the host's restatement of the kernel's schedule, every column: rows j >= c of column c, the other triangle left zero
+        std::vector<double> col((size_t)n);
+        std::fill(out, out + (size_t)n * n, 0.0);
+        for (int c = 0; c < n; ++c) {
+            SupernodalLDLT::emulate_device_column(E, c, col.data());
+            for (int j = c; j < n; ++j) out[(size_t)j * n + c] = col[(size_t)j];
+        }
+        return GMG_OK;
+    }
+    PoolScope pool_scope_(&h->pool);
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, GMG_ERR_HIP, "hipSetDevice failed");
+    DevBuf<double> X, dst;
+    CoarseInverseRun run;
+    int rc;
+    const int follow = mode == 1 ? kInvFollowMirror : mode == 2 ? kInvFollowPermute : mode == 3 ? kInvFollowScatter : kInvFollowTriangle;
+    if (mode == 2 && n > kInvPermuteLdsMax) return fail(h, GMG_ERR_INVALID, "rows of this length do not fit the LDS: mode 3");
+    // (as in the set-up the destination is not cleared: columns n .. lda - 1 of the full inverse are never written and mean nothing)
+    if (mode != 1 && (rc = dev_alloc(h, dst, (size_t)info[12]))) return rc;
+    if ((rc = coarse_inverse_core(h, E, w, follow, X, dst.get(), lda, run))) { (void)hipStreamSynchronize(h->stream); return rc; }
+    return d2h(h, out, mode == 1 ? X.get() : dst.get(), sizeof(double) * (size_t)info[12]);
+} GMG_CATCH_H
+
 int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const double* val, int mode, int block_rows, int sigma, int64_t* info,
                         int* new2old, int* color_begin, int* blk_begin, unsigned char* row_color) try {
     if (n <= 0 || !colptr || !rowidx || !val || mode < 0 || mode > 4) return GMG_ERR_INVALID;

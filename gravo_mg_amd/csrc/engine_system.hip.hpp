@@ -121,23 +121,22 @@ bool want_coarse_device(gmg_handle h, int n_coarse) {
 bool want_coarse_triangle(gmg_handle h) { return h->cfg.coarse_mode == GMG_COARSE_DEVICE_TRIANGLE; }
 
 // Dense inverse of the coarsest operator, built ON THE DEVICE from the host's sparse factor (setup_kernels.hip.hpp::coarse_inverse_tiles): the factor
-// goes up in the device's chunk layout (a few MB), one launch carries every 64-column tile of the identity through it, a second one mirrors the
+// goes up in the device's chunk layout (a few MB), one launch carries every tile of the identity (16, 32 or 64 columns: coarse_inverse_width) through it, a second one mirrors the
 // lower triangle, a third one moves it from the factor's numbering into the level's.  (Until round 6 the host solved n_L right-hand sides one by
 // one: 188 - 226 ms of set-up at n_L = 6 005.)
 // GMG_COARSE_DEVICE_TRIANGLE stops after the tiles: one launch packs the triangle they computed into 64 x 64 blocks, still in the factor's numbering
 // (setup_kernels.hip.hpp::pack_lower_blocks); the full matrix is not made, the permutation stays on the device for the product, and the product's
 // scratch is allocated here.
-int build_coarse_inverse_device(gmg_handle h) {
+// The core: one exported factor, one tile width (16 / 32 / 64), one choice of follow-up kernels, destinations the caller owns.  X (n x n, the
+// inverse in the factor's numbering) is allocated here and handed back; dst: the full inverse in the level's numbering (leading dimension
+// ldo) for kInvFollowPermute / kInvFollowScatter, the packed triangle for kInvFollowTriangle, unused for kInvFollowMirror (X with both triangles
+// is the result).  Of the handle only the stream, the pool, the bounce buffers and the two scratch events are used: gmg_debug_coarse_inverse
+// runs this on a caller's matrix.
+enum { kInvFollowPermute = 0, kInvFollowScatter = 1, kInvFollowTriangle = 2, kInvFollowMirror = 3 };
+struct CoarseInverseRun { double upload_ms = 0.0; float tiles_ms = 0.f; bool timed = false; };
+int coarse_inverse_core(gmg_handle h, const SupernodalLDLT::DeviceFactor& E, int width, int follow, DevBuf<double>& X, double* dst, int ldo, CoarseInverseRun& run) {
     auto t0 = clk::now();
-    const int nl = h->coarse.n;
-    const bool tri_mode = want_coarse_triangle(h);
-    h->coarse_triangle = tri_mode;
-    SupernodalLDLT::DeviceFactor E;
-    h->coarse.export_device_factor(E);
-    h->timing["coarse_inverse_export_ms"] = ms_since(t0);
-    // tile width: enough workgroups for the chip's compute units (121 tiles of 16 columns at n_L = 1 929, 376 at 6 005: two 1024-thread
-    // workgroups per compute unit are resident), wider tiles only where there would be more tiles than that
-    const int width = nl <= 8192 ? 16 : (nl <= 16384 ? 32 : 64);
+    const int nl = E.n;
     std::vector<int> tile_ptr_h, tile_q_h;
     E.tile_paths(width, tile_ptr_h, tile_q_h);
     const std::vector<int> lev_big_h = E.big_per_level(gmgs::kInvBigRows);
@@ -153,13 +152,61 @@ int build_coarse_inverse_device(gmg_handle h) {
     if ((rc = upload(h, lev_meta, lev_meta_h)) || (rc = upload(h, tile_meta, tile_meta_h)) || (rc = upload(h, rows, E.rows)) || (rc = upload(h, lev_ptr, E.lev_ptr)) || (rc = upload(h, lev_big, lev_big_h)) ||
         (rc = upload(h, tile_ptr, tile_ptr_h)) || (rc = upload(h, vals, E.vals)) || (rc = upload(h, tri, E.tri)) || (rc = upload(h, dinv, E.dinv)))
         return rc;
+    const bool permuted = follow == kInvFollowPermute || follow == kInvFollowScatter;
     std::vector<int> inv_h((size_t)nl);
     for (int i = 0; i < nl; ++i) inv_h[(size_t)E.perm[(size_t)i]] = i;
     DevBuf<int> perm_d, inv_d;
-    if (!tri_mode && ((rc = upload(h, perm_d, E.perm)) || (rc = upload(h, inv_d, inv_h)))) return rc;
+    if (permuted && ((rc = upload(h, perm_d, E.perm)) || (rc = upload(h, inv_d, inv_h)))) return rc;
     const size_t bytes = sizeof(double) * (size_t)nl * nl;
-    DevBuf<double> X;                                       // the inverse in the factor's numbering
     if ((rc = dev_alloc(h, X, (size_t)nl * nl))) return rc;
+    HIPCHK(hipMemsetAsync(X, 0, bytes, h->stream));
+    gmgs::InvFactor F;
+    F.n = nl; F.nq = E.nq; F.nlev = E.nlev;
+    F.lev_meta = lev_meta; F.tile_meta = tile_meta; F.rows = rows; F.lev_ptr = lev_ptr; F.lev_big = lev_big; F.tile_ptr = tile_ptr;
+    F.vals = vals; F.tri = tri; F.dinv = dinv;
+    static_assert(gmgs::kInvChunk == SupernodalLDLT::kChunk, "chunk width of the exported factor");
+    const int nt = (nl + width - 1) / width, nm = (nl + 63) / 64;
+    const int nb = tri_blocks(nl);
+    run.upload_ms = ms_since(t0);
+    if (nl > 0) {
+        (void)hipEventRecord(h->ev0, h->stream);
+        const dim3 block(64 * gmgs::kInvWaves);
+        if (width == 16) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<16>, dim3(nt), block, 0, h->stream, F, X.get());
+        else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.get());
+        else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.get());
+        (void)hipEventRecord(h->ev1, h->stream);
+        if (follow == kInvFollowTriangle) {
+            hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X, nl, dst);
+        } else {
+            hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.get(), nl);
+            // ... and into the level's numbering: the product kernel then reads its vectors contiguously
+            if (follow == kInvFollowPermute) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X, (const int*)perm_d, (const int*)inv_d, nl, dst, ldo);
+            else if (follow == kInvFollowScatter) hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X, (const int*)perm_d, nl, dst, ldo);
+        }
+    }
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(h->stream));        // (the temporaries above go back to the pool)
+    run.timed = nl > 0 && hipEventElapsedTime(&run.tiles_ms, h->ev0, h->ev1) == hipSuccess;
+    return GMG_OK;
+}
+
+// tile width: enough workgroups for the chip's compute units (121 tiles of 16 columns at n_L = 1 929, 376 at 6 005: two 1024-thread
+// workgroups per compute unit are resident), wider tiles only where there would be more tiles than that
+inline int coarse_inverse_width(int nl) { return nl <= 8192 ? 16 : (nl <= 16384 ? 32 : 64); }
+// rows of the inverse that fit the LDS go through permute_symmetric, longer ones through permute_symmetric_scatter
+constexpr int kInvPermuteLdsMax = 8192;
+
+// The set-up's wrapper: the handle's own factor, the width rule, the handle's d_ainv or d_tri as destination, the timing keys.
+int build_coarse_inverse_device(gmg_handle h) {
+    auto t0 = clk::now();
+    const int nl = h->coarse.n;
+    const bool tri_mode = want_coarse_triangle(h);
+    h->coarse_triangle = tri_mode;
+    SupernodalLDLT::DeviceFactor E;
+    h->coarse.export_device_factor(E);
+    h->timing["coarse_inverse_export_ms"] = ms_since(t0);
+    const int width = coarse_inverse_width(nl);
+    int rc;
     const int lda = (nl + 7) / 8 * 8;
     const int nb = tri_blocks(nl);
     if (tri_mode) {
@@ -178,36 +225,21 @@ int build_coarse_inverse_device(gmg_handle h) {
         h->ainv_n = nl; h->ainv_ld = lda;
         h->timing["coarse_inverse_bytes"] = (double)(sizeof(double) * (size_t)nl * lda);
     }
-    HIPCHK(hipMemsetAsync(X, 0, bytes, h->stream));
-    gmgs::InvFactor F;
-    F.n = nl; F.nq = E.nq; F.nlev = E.nlev;
-    F.lev_meta = lev_meta; F.tile_meta = tile_meta; F.rows = rows; F.lev_ptr = lev_ptr; F.lev_big = lev_big; F.tile_ptr = tile_ptr;
-    F.vals = vals; F.tri = tri; F.dinv = dinv;
-    static_assert(gmgs::kInvChunk == SupernodalLDLT::kChunk, "chunk width of the exported factor");
-    const int nt = (nl + width - 1) / width, nm = (nl + 63) / 64;
-    h->timing["coarse_inverse_upload_ms"] = ms_since(t0) - h->timing["coarse_inverse_export_ms"];
-    if (nl > 0) {
-        (void)hipEventRecord(h->ev0, h->stream);
-        const dim3 block(64 * gmgs::kInvWaves);
-        if (width == 16) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<16>, dim3(nt), block, 0, h->stream, F, X.get());
-        else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.get());
-        else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.get());
-        (void)hipEventRecord(h->ev1, h->stream);
-        if (tri_mode) {
-            hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X, nl, h->d_tri);
-        } else {
-            hipLaunchKernelGGL(gmgs::mirror_lower_to_upper, dim3(nm, nm), dim3(256), 0, h->stream, X.get(), nl);
-            // ... and into the level's numbering: the product kernel then reads its vectors contiguously
-            if (nl <= 8192) hipLaunchKernelGGL(gmgs::permute_symmetric, dim3(nl), dim3(256), sizeof(double) * (size_t)nl, h->stream, (const double*)X, (const int*)perm_d, (const int*)inv_d, nl, h->d_ainv, lda);
-            else hipLaunchKernelGGL(gmgs::permute_symmetric_scatter, dim3(nl), dim3(256), 0, h->stream, (const double*)X, (const int*)perm_d, nl, h->d_ainv, lda);
-        }
-    }
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(h->stream));        // (the temporaries above go back to the pool; the host copy E dies here)
-    if (nl > 0) { float ms = 0.f; if (hipEventElapsedTime(&ms, h->ev0, h->ev1) == hipSuccess) h->timing["coarse_inverse_tiles_ms"] = ms; }
+    DevBuf<double> X;                                       // the inverse in the factor's numbering
+    CoarseInverseRun run;
+    const int follow = tri_mode ? kInvFollowTriangle : (nl <= kInvPermuteLdsMax ? kInvFollowPermute : kInvFollowScatter);
+    const double before = ms_since(t0);
+    if ((rc = coarse_inverse_core(h, E, width, follow, X, tri_mode ? h->d_tri.get() : h->d_ainv.get(), lda, run))) return rc;
+    h->timing["coarse_inverse_upload_ms"] = before + run.upload_ms - h->timing["coarse_inverse_export_ms"];
+    if (run.timed) h->timing["coarse_inverse_tiles_ms"] = run.tiles_ms;
     h->timing["coarse_inverse_ms"] = ms_since(t0);
     h->timing["coarse_inverse_levels"] = E.nlev;
     h->timing["coarse_inverse_chunks"] = E.nq;
+    long long shape[10];
+    E.shape_info(width, gmgs::kInvBigRows, shape);
+    h->timing["coarse_inverse_width"] = (double)shape[3];
+    h->timing["coarse_inverse_big_chunks"] = (double)shape[4];
+    h->timing["coarse_inverse_max_level_chunks"] = (double)shape[5];
     return GMG_OK;
 }
 

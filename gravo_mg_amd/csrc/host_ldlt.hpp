@@ -737,6 +737,25 @@ public:
                 tile_ptr[(size_t)t + 1] = (int)tile_q.size();
             }
         }
+        // Which branches of the device kernel this factor reaches at tile width `width` (gmg_debug_coarse_inverse's info[], the timing keys
+        // coarse_inverse_width / _big_chunks / _max_level_chunks): out[0..9] = chunks, levels, tiles, width, chunks with >= big_rows rows below
+        // them, most chunks with fewer in one level, most rows below one chunk, most rows below a chunk with fewer than big_rows, chunks
+        // narrower than kChunk, chunks of level 0 (the roots).
+        void shape_info(int width, int big_rows, long long out[10]) const {
+            for (int k = 0; k < 10; ++k) out[k] = 0;
+            out[0] = nq; out[1] = nlev; out[2] = (n + width - 1) / width; out[3] = width;
+            for (int v = 0; v < nlev; ++v) {
+                long long small = 0;
+                for (int k = lev_ptr[(size_t)v]; k < lev_ptr[(size_t)v + 1]; ++k) {
+                    const int q = lev_q[(size_t)k], r = q_rptr[(size_t)q + 1] - q_rptr[(size_t)q];
+                    out[6] = std::max<long long>(out[6], r);
+                    if (r >= big_rows) ++out[4]; else { ++small; out[7] = std::max<long long>(out[7], r); }
+                }
+                out[5] = std::max(out[5], small);
+            }
+            for (int q = 0; q < nq; ++q) if (q_w[(size_t)q] < kChunk) ++out[8];
+            out[9] = nlev ? lev_ptr[1] - lev_ptr[0] : 0;
+        }
         std::vector<double> vals, tri, dinv;
     };
     // Column c (factor numbering) of A^-1 in rows >= c, by the algorithm of the device kernel on the exported layout -- way down in push form along the

@@ -766,15 +766,16 @@ __global__ __launch_bounds__(64) void rap_rows(const int* __restrict__ a_ptr, co
 // turns the per-cycle part into ONE dense symmetric matrix-vector product on the device -- no host round trip inside the cycle.)
 // X = A_L^-1 = P^T (L^-T D^-1 L^-1) P, computed in the FACTOR's numbering (GMG_COARSE_DEVICE_TRIANGLE keeps it there -- its product permutes the vectors; GMG_COARSE_DEVICE_INVERSE
 // moves it into the level's afterwards): n right-hand sides e_c,
-// every one an independent pair of sparse triangular solves.  One workgroup owns a TILE of 64 columns c (one lane per column: a row of X
-// restricted to the tile is 512 contiguous bytes) and carries it through the whole factor:
+// every one an independent pair of sparse triangular solves.  One workgroup owns a TILE of W = 16, 32 or 64 columns c (the host picks W from
+// n: 16 up to 8 192, 32 up to 16 384, 64 beyond; a row of X restricted to the tile is 8 W contiguous bytes, and a wave covers 64 / W such rows
+// with one load) and carries it through the whole factor:
 //   * down (L y = e_c): y is nonzero only at ancestors of c in the elimination tree, so only chunks whose subtree meets the tile are visited
 //     (q_fdesc); one wave walks them in ascending order -- push form: the chunk's own columns are finished in registers, then every row below
 //     receives its update (a lane only ever re-reads what it wrote itself: program order);
 //   * up (L^T x = D^-1 y), needed for rows j >= c only (the inverse is symmetric; the other triangle is mirrored afterwards): pull form by
 //     LEVELS of the elimination tree from the roots down, the chunks of a level dealt to the workgroup's waves, a barrier per level.
 // Every entry of X is produced by one lane with a fixed order of operations: the result is deterministic (ranks of a multi-GPU job that
-// replicate the coarsest level get the same bits).  Traffic: a tile reads sum(rows of the chunks) x 512 B per pass from its own 64-column slab,
+// replicate the coarsest level get the same bits).  Traffic: a tile reads sum(rows of the chunks) x 8 W bytes per pass from its own W-column slab,
 // which the L2 / memory-side cache serve; arithmetic nnz(L) x n fused multiply-adds in all -- microseconds of the chip's fp64 rate, which is why
 // the build is latency-bound (one dependent global round trip per level) and not a candidate for MFMA.
 struct InvFactor {

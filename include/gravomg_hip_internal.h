@@ -88,6 +88,30 @@ int gmg_debug_device_galerkin(gmg_handle h, int n, const int* a_colptr, const in
                               const int* u_colptr, const int* u_rowidx, const double* u_val, int64_t cap, int* c_colptr, int* c_rowidx, double* c_val,
                               double* c_val2, int* status);
 
+/* The DEVICE-BUILT dense inverse of a coarsest operator (csrc/setup_kernels.hip.hpp::coarse_inverse_tiles and its follow-up kernels) on a matrix
+ * the caller builds by hand, through the code the set-up runs -- factorisation, export of the factor in the device's chunk layout, upload, the
+ * tiles launch, mirror / permutation / packing (csrc/engine_system.hip.hpp::coarse_inverse_core) -- into buffers of its own: the handle lends its
+ * stream and its pool and is otherwise left alone (hierarchy, system, d_ainv, d_tri and timing keys untouched; no kernel launch that the set-up
+ * does not make).  A: n x n symmetric positive definite, CSC as stored, every index checked (GMG_ERR_INVALID; GMG_ERR_NUMERIC when the
+ * factorisation fails).  width: 0 = the set-up's rule (16 up to n = 8 192, 32 up to 16 384, 64 beyond), or 16 / 32 / 64 to force that
+ * instantiation.  mode:
+ *   0  host only (h may be NULL): SupernodalLDLT::emulate_device_column for every column of the same export; out n x n row-major, factor's
+ *      numbering, entry [j][c] for j >= c, the other triangle zero
+ *   1  device: X in the factor's numbering after mirror_lower_to_upper, n x n row-major
+ *   2  device: the full inverse in the level's numbering through permute_symmetric, n rows of info[13] doubles (columns >= n mean nothing);
+ *      GMG_ERR_INVALID for n > 8 192
+ *   3  as 2 through permute_symmetric_scatter, whatever n is
+ *   4  device: the packed triangle of pack_lower_blocks (csrc/coarse_triangle.hpp), info[12] doubles
+ * Modes 1 .. 4 return GMG_ERR_NO_DEVICE without a HIP device.  info[0..15]: chunks, levels, tiles, width used, chunks with at least kInvBigRows
+ * rows below them (worked off by all waves), most other chunks in one level, most rows below one chunk, most rows below one chunk of the other
+ * kind, chunks narrower than 8 columns, chunks of level 0 (roots), row entries of all chunks, entries of tile_q, doubles of `out` for this mode,
+ * its leading dimension, kInvBigRows, kInvWaves.  out == NULL: info and the optional arrays only (the sizing call).  The exported factor as the
+ * kernel reads it, each array optional: perm n (factor -> level), q_col0 / q_w / lev_q `chunks`, q_rptr chunks + 1, rows info[10], vals
+ * 8 info[10], tri 64 chunks, dinv n, lev_ptr levels + 1, lev_big levels (at kInvBigRows), tile_ptr tiles + 1 and tile_q info[11] for the width used. */
+int gmg_debug_coarse_inverse(gmg_handle h, int n, const int* colptr, const int* rowidx, const double* val, int width, int mode, double* out, int64_t out_cap,
+                             int64_t* info, int* perm, int* q_col0, int* q_w, int* q_rptr, int* rows, double* vals, double* tri, double* dinv, int* lev_ptr,
+                             int* lev_q, int* lev_big, int* tile_ptr, int* tile_q);
+
 /* Host-only view of the device layout planner (colouring / block growing / SELL-64), for CPU tests of the
  * host logic.  mode 0: colour-major ordering (exact multicolour Gauss-Seidel), mode 1: block ordering
  * (block-hybrid Gauss-Seidel, `block_rows` rows per block), mode 2: mode 0 with the locality reordering forced (rows of a colour in breadth-first

@@ -423,7 +423,7 @@ def test_block_sweeps_with_blocks_beyond_the_register_windows(cabi, oracle):
 @pytest.mark.parametrize("n1,n2,kind,lower_bound", [(190, 190, "smoothing", 1000), (300, 280, "poisson", 1000), (130, 120, "poisson", 300), (64, 60, "poisson", 20)])
 def test_device_built_coarse_inverse_against_the_host_factor(cabi, oracle, n1, n2, kind, lower_bound):
     """The dense inverse of the coarsest operator is built ON THE DEVICE from the host's sparse LDL^T factor (setup_kernels.hip.hpp::coarse_inverse_tiles:
-    every 64-column tile of the identity through the factor, lower triangle mirrored) and applied with the vectors permuted into the factor's
+    every 16-column tile of the identity through the factor at these sizes, lower triangle mirrored) and applied with the vectors permuted into the factor's
     numbering (gmgk::dense_symv).  Against the host back-substitution with the same factor (GMG_COARSE_HOST_LDLT) and the oracle's coarse solve
     (multigrid_solver.cpp:1075, 1401), at coarsest sizes from one tile to ~6 000 unknowns (94 tiles, the demos' size), three right-hand sides; two
     handles build the same bits (ranks of a multi-GPU job replicate this level)."""
