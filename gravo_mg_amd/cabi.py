@@ -44,7 +44,7 @@ class GmgConfig(C.Structure):
         ("row_align", C.c_int), ("block_rows", C.c_int), ("block_lanes", C.c_int), ("block_from_level", C.c_int),
         ("device_setup", C.c_int), ("device_rap", C.c_int), ("reorder_fine", C.c_int), ("inner_precision", C.c_int), ("block_csr", C.c_int), ("host_threads", C.c_int),
         ("verbose", C.c_int), ("gs_omega", C.c_double), ("restrict_sigma", C.c_int), ("block_ep", C.c_int), ("dist_shard_levels", C.c_int), ("block_fine", C.c_int), ("fine_col16", C.c_int), ("stream_gate", C.c_int), ("dist_exchange", C.c_int), ("prepare_structure", C.c_int), ("fuse_restrict_sweep", C.c_int), ("speculate_head", C.c_int), ("uniform_slices", C.c_int), ("color_ahead", C.c_int),
-        ("fold_head", C.c_int), ("accelerate", C.c_int),
+        ("fold_head", C.c_int), ("device_coloring", C.c_int), ("accelerate", C.c_int),
     ]
 
 
@@ -163,6 +163,8 @@ INTERNAL_SIGNATURES = {
     "gmg_host_plan_level": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _ip, _ip, _ip,
                                       C.POINTER(C.c_ubyte)]),
     "gmg_host_fine_block_rule": (C.c_int, [C.c_int, _ip, _ip, _dp, _ip, _ip]),
+    "gmg_jp_coloring_host": (C.c_int, [C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip]),
+    "gmg_jp_coloring_device": (C.c_int, [_vp, C.c_int, _ip, _ip, C.POINTER(C.c_ubyte), _ip, _ip]),
     "gmg_debug_set": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "gmg_debug_f32_op": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp]),
     "gmg_bench_kernel": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip]),
@@ -352,7 +354,7 @@ class Engine:
 
     def __init__(self, smoother=SMOOTHER_MULTICOLOR_GS, pre_iters=2, post_iters=2, jacobi_omega=0.67,
                  coarse_mode=COARSE_AUTO, use_graph=False, sigma=0, row_align=64, block_rows=64, block_from_level=1, block_lanes=0,
-                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None):
+                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None, device_coloring=None):
         l = lib()
         cfg = GmgConfig()
         l.gmg_config_default(C.byref(cfg))
@@ -391,6 +393,8 @@ class Engine:
         cfg.accelerate = int(accelerate)          # 0: the plain loop; 1..4: truncated GCR around the V-cycle (gmg_config::accelerate)
         if fold_head is not None:
             cfg.fold_head = int(bool(fold_head))
+        if device_coloring is not None:
+            cfg.device_coloring = int(device_coloring)       # 0 / 1; anything else is refused by gmg_create (gmg_config::device_coloring)
         self._h = _vp()
         rc = l.gmg_create(C.byref(cfg), C.byref(self._h))
         if rc:
@@ -1039,6 +1043,25 @@ def host_fine_block_rule(A):
     if rc:
         raise GmgError(rc, "gmg_host_fine_block_rule")
     return bool(blocked.value), int(reason.value)
+
+
+def jp_coloring(indptr, indices, eng: "Engine" = None):
+    """(colours, n_colors, rounds) of the Jones-Plassmann colouring behind gmg_config::device_coloring on the symmetric pattern (indptr, indices),
+    taken exactly as given (int32, no canonicalisation): by the host specification (gmg_jp_coloring_host), or with `eng` by the device kernels
+    (gmg_jp_coloring_device; the engine lends its stream and pool).  n_colors = -1: 254 colours do not suffice (colours is None, rounds 0)."""
+    indptr = np.ascontiguousarray(indptr, np.int32); indices = np.ascontiguousarray(indices, np.int32)
+    n = len(indptr) - 1
+    idx = indices if len(indices) else np.zeros(1, np.int32)
+    colours = np.full(max(n, 1), 255, np.uint8)
+    ncol, rounds = C.c_int(0), C.c_int(0)
+    out = colours.ctypes.data_as(C.POINTER(C.c_ubyte))
+    if eng is None:
+        rc = lib().gmg_jp_coloring_host(n, _pi(indptr), _pi(idx), out, C.byref(ncol), C.byref(rounds))
+        if rc:
+            raise GmgError(rc, "gmg_jp_coloring_host")
+    else:
+        eng._chk(lib().gmg_jp_coloring_device(eng._h, n, _pi(indptr), _pi(idx), out, C.byref(ncol), C.byref(rounds)))
+    return (colours[:n] if ncol.value >= 0 else None), int(ncol.value), int(rounds.value)
 
 
 def host_ldlt_solve(A, b):

@@ -338,6 +338,7 @@ public:
         else if (key == "inner_precision") c.inner_precision = (int)value;
         else if (key == "accelerate") c.accelerate = (int)value;
         else if (key == "fold_head") c.fold_head = (int)value;
+        else if (key == "device_coloring") c.device_coloring = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

@@ -140,6 +140,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->fold_head = 1;
     cfg->uniform_slices = 1;
     cfg->color_ahead = 1;
+    cfg->device_coloring = 0; // level 0 is coloured by the host's greedy loop (1: Jones-Plassmann rounds on the device, another colouring: see gmg_config)
     cfg->dist_exchange = 0;
     cfg->block_fine = 1;      // level 0 blocked too where it pays and is safe (long rows, Stieltjes matrix): see gmg_config
     cfg->restrict_sigma = 64;
@@ -165,6 +166,7 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
         c.reorder_fine < 0 || c.reorder_fine > 2 || c.inner_precision < 0 || c.inner_precision > 1 || c.block_rows < 0 || c.block_rows > gmgk::kBlockRows || c.block_rows % 64 || c.block_from_level < 0 || !(c.gs_omega > 0.0 && c.gs_omega < 2.0) || c.dist_shard_levels < 1 || c.dist_shard_levels > 2 || c.block_fine < 0 || c.block_fine > 1 || c.dist_exchange < 0 || c.dist_exchange > 2 ||
         (c.block_lanes != 0 && c.block_lanes != 1 && c.block_lanes != 4) || (c.block_lanes != 1 && c.block_rows > gmgk::kQuadBlockRows)) return GMG_ERR_INVALID;
     if (c.accelerate < 0 || c.accelerate > gmg::kAccelMaxDepth) return GMG_ERR_INVALID;
+    if (c.device_coloring < 0 || c.device_coloring > 1) return GMG_ERR_INVALID;
     if (c.smoother < GMG_SMOOTHER_MULTICOLOR_GS || c.smoother > GMG_SMOOTHER_CHEBYSHEV) return GMG_ERR_INVALID;
     if (c.accelerate > 0 && c.inner_precision) return GMG_ERR_UNSUPPORTED;      // the recombination is fp64 only (gmg_config::accelerate)
     gmg_handle h = new gmg_solver_s();
@@ -1637,6 +1639,40 @@ int gmg_debug_device_galerkin(gmg_handle h, int n, const int* a_colptr, const in
         if ((int64_t)C2.val.size() != nnz) return fail(h, GMG_ERR_STATE, "the numeric pass returned another number of entries");
         if (nnz) std::memcpy(c_val2, C2.val.data(), sizeof(double) * (size_t)nnz);
     }
+    return GMG_OK;
+} GMG_CATCH_H
+
+// Test access to the colouring of gmg_config::device_coloring (gravomg_hip_internal.h): the specification on the host, and the set-up's own
+// device_jp_coloring on a pattern of the caller's.  Of the handle only the stream, the pool and the bounce buffers are used.
+static bool jp_pattern_ok(int n, const int* colptr, const int* rowidx) {
+    if (n <= 0 || !colptr || !rowidx || colptr[0] != 0) return false;
+    for (int i = 0; i < n; ++i) if (colptr[i + 1] < colptr[i]) return false;
+    for (int q = 0; q < colptr[n]; ++q) if (rowidx[q] < 0 || rowidx[q] >= n) return false;      // every index the kernels and the host loop follow
+    return true;
+}
+int gmg_jp_coloring_host(int n, const int* colptr, const int* rowidx, unsigned char* colours, int* n_colors, int* rounds) try {
+    if (!colours || !n_colors || !rounds || !jp_pattern_ok(n, colptr, rowidx)) return GMG_ERR_INVALID;
+    RawVec<unsigned char> c8;
+    *n_colors = jp_coloring_host(PatternView{n, colptr, rowidx}, c8, rounds);
+    if (*n_colors >= 0) std::memcpy(colours, c8.data(), (size_t)n);
+    return GMG_OK;
+} GMG_CATCH_0
+
+int gmg_jp_coloring_device(gmg_handle h, int n, const int* colptr, const int* rowidx, unsigned char* colours, int* n_colors, int* rounds) try {
+    NEED_DEVICE();
+    if (!colours || !n_colors || !rounds || !jp_pattern_ok(n, colptr, rowidx)) return fail(h, GMG_ERR_INVALID, "bad arguments");
+    if (hipSetDevice(h->cfg.device) != hipSuccess) return fail(h, GMG_ERR_HIP, "hipSetDevice failed");
+    DevBuf<int> d_ptr, d_idx;
+    DevBuf<unsigned char> d_c8;
+    const size_t nnz = (size_t)colptr[n];
+    int rc;
+    if ((rc = dev_alloc(h, d_ptr, (size_t)n + 1)) || (rc = dev_alloc(h, d_idx, nnz)) || (rc = h2d(h, d_ptr, colptr, sizeof(int) * ((size_t)n + 1))) ||
+        (nnz && (rc = h2d(h, d_idx, rowidx, sizeof(int) * nnz))) || (rc = device_jp_coloring(h, d_ptr, d_idx, n, d_c8, n_colors, rounds))) {
+        (void)hipStreamSynchronize(h->stream);
+        return rc;
+    }
+    if (*n_colors >= 0 && (rc = d2h(h, colours, d_c8, (size_t)n))) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
     return GMG_OK;
 } GMG_CATCH_H
 

@@ -179,6 +179,51 @@ int device_permute_pattern(gmg_handle h, const DevCsr& dA, int n, int64_t nnz) {
     return GMG_OK;
 }
 
+// Colour bytes of a symmetric pattern made on the device (gmg_config::device_coloring; setup_kernels.hip.hpp::jp_round, specification:
+// host_plan.hpp::jp_coloring_host): one launch per round.  The first kJpFullRounds rounds run over all rows -- most vertices are still uncoloured
+// and a worklist would be the identity -- the later ones over a worklist of the uncoloured vertices, compacted again after every kJpBatch rounds;
+// with the compaction's count the host reads back 16 bytes, which is how it learns that nobody is left: one round trip per batch, not per round.
+// Every round colours at least the uncoloured vertex of largest priority, so n rounds without an end are an error, not a loop.
+// d_c8: n bytes, 255 = none.  *n_colors = -1: 254 colours do not suffice (d_c8 is unusable; *rounds = 0).
+constexpr int kJpFullRounds = 4, kJpBatch = 4;
+int device_jp_coloring(gmg_handle h, const int* d_ptr, const int* d_idx, int n, DevBuf<unsigned char>& d_c8, int* n_colors, int* rounds) {
+    DevBuf<unsigned> st, ctl;
+    DevBuf<int> cur, next;
+    int rc;
+    if ((rc = dev_alloc(h, st, (size_t)n)) || (rc = dev_alloc(h, d_c8, (size_t)n)) || (rc = dev_alloc(h, ctl, 4)) || (rc = dev_alloc(h, cur, (size_t)n))) return rc;
+    HIPCHK(hipMemsetAsync(st, 0, sizeof(unsigned) * (size_t)n, h->stream));
+    HIPCHK(hipMemsetAsync(d_c8, 255, (size_t)n, h->stream));
+    HIPCHK(hipMemsetAsync(ctl, 0, sizeof(unsigned) * 4, h->stream));
+    auto blocks = [](int count) { return dim3((unsigned)((count + gmgs::kJpBlock - 1) / gmgs::kJpBlock)); };
+    unsigned host_ctl[4] = {0, 0, 0, 0};
+    // the compaction of `src` (count entries; null: all rows) into `dst`, and the read-back behind it
+    auto compact = [&](const int* src, int count, int* dst) -> int {
+        HIPCHK(hipMemsetAsync(ctl, 0, sizeof(unsigned), h->stream));
+        hipLaunchKernelGGL(gmgs::jp_compact, blocks(count), dim3(gmgs::kJpBlock), 0, h->stream, src, count, (const unsigned*)st, dst, ctl.get());
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(host_ctl, ctl, sizeof host_ctl, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        return GMG_OK;
+    };
+    unsigned r = 0;
+    for (; r < (unsigned)kJpFullRounds; ++r)
+        hipLaunchKernelGGL(gmgs::jp_round, blocks(n), dim3(gmgs::kJpBlock), 0, h->stream, d_ptr, d_idx, n, (const int*)nullptr, n, r + 1, st.get(), d_c8.get(), ctl.get());
+    if ((rc = compact(nullptr, n, cur))) return rc;
+    int left = (int)host_ctl[0];
+    while (left > 0 && !host_ctl[3]) {
+        if (left > n || r >= (unsigned)n || r >= (1u << 24) - (unsigned)kJpBatch - 1u) return fail(h, GMG_ERR_STATE, "the device colouring did not finish within n rounds");
+        if (!next && (rc = dev_alloc(h, next, (size_t)left))) return rc;      // (the lists only shrink: after the first swap `next` is the longer one)
+        for (int k = 0; k < kJpBatch; ++k, ++r)
+            hipLaunchKernelGGL(gmgs::jp_round, blocks(left), dim3(gmgs::kJpBlock), 0, h->stream, d_ptr, d_idx, n, (const int*)cur, left, r + 1, st.get(), d_c8.get(), ctl.get());
+        if ((rc = compact(cur, left, next))) return rc;
+        std::swap(cur, next);
+        left = (int)host_ctl[0];
+    }
+    *n_colors = host_ctl[3] ? -1 : (int)host_ctl[2];
+    *rounds = host_ctl[3] ? 0 : (int)host_ctl[1];
+    return GMG_OK;
+}
+
 // Host copy of A_k (natural numbering), on demand: the device keeps the master copy (Level::dA).
 int ensure_host_A(gmg_handle h, int k, bool values) {
     Level& l = h->lv[k];

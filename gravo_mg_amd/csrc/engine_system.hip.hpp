@@ -670,6 +670,7 @@ private:
         reorder0 = mc && !ord_hit && !blocked0 && wants_locality_reorder(PatternView{n, colptr, rowidx}, h->cfg.reorder_fine);
         if (reorder0) e.ahead.cancel();                // (the level is coloured along another visit order: the loop started on the caller's order is of no use)
         if (e.early_A0.ptr && device_setup && h->cfg.device_rap) { h->lv[0].dA = std::move(e.early_A0); e.early_A0 = {}; A0_uploaded = true; }
+        { const int rc = color_level0_on_device(); if (rc != GMG_OK) return rc; }
         // (h->cluster_order is only read once the patches are ready: build_patches may still be writing it)
         const bool have_bfs = (int)h->bfs_order.size() == n, have_cluster = h->patches_ready && (int)h->cluster_order.size() == n;
         h->base_order_choice = (reorder0 && h->patches_ready && have_bfs && !have_cluster) ? 1 : 0;
@@ -686,11 +687,50 @@ private:
         if (reorder0 && device_setup && h->cfg.device_rap && (have_cluster || (h->patches_ready && have_bfs))) {
             int rc = A0_uploaded ? GMG_OK : upload_csr_raw(h, h->lv[0].dA, n, colptr, rowidx, val);
             if (rc == GMG_OK) { A0_uploaded = true; rc = choose_base_order(h, h->lv[0].dA, n); }
-            if (rc == GMG_OK) rc = device_permute_pattern(h, h->lv[0].dA, n, colptr[n]);
+            // (colours from the device depend on no visit order: the pattern need not come back permuted for a host loop to walk it)
+            if (rc == GMG_OK && !colored_dev) rc = device_permute_pattern(h, h->lv[0].dA, n, colptr[n]);
             if (rc != GMG_OK) return rc;
-            permuted0 = true;
-            mark("permuted_pattern");
+            permuted0 = !colored_dev;
+            if (permuted0) mark("permuted_pattern");
         }
+        return GMG_OK;
+    }
+    // gmg_config::device_coloring: the colour bytes of level 0 from the device (engine_setup.hip.hpp::device_jp_coloring), enqueued as soon as A_0 is
+    // there and copied back (n bytes) for make_ordering.  Only where a new colour-major ordering of level 0 is due and the set-up runs on the
+    // device; every other case, 254 colours that do not suffice and a failure of the device colouring leave the host's greedy colouring in charge,
+    // with the results of device_coloring = 0.  Timing keys "colored_on_device", "device_coloring_ms", "device_coloring_rounds".
+    int color_level0_on_device() {
+        h->timing["colored_on_device"] = 0.0; h->timing["device_coloring_ms"] = 0.0; h->timing["device_coloring_rounds"] = 0.0;
+        const bool colour_major0 = !blocked0 && !(h->cfg.block_rows > 0 && h->cfg.block_from_level <= 0);
+        if (!h->cfg.device_coloring || ord_hit || !mc || !colour_major0 || !device_setup || !h->cfg.device_rap) return GMG_OK;
+        if (!A0_uploaded) {
+            const int rc = upload_csr_raw(h, h->lv[0].dA, n, colptr, rowidx, val);
+            if (rc != GMG_OK) return rc;
+            A0_uploaded = true;
+        }
+        auto tc = clk::now();
+        DevBuf<unsigned char> d_c8;
+        int ncol = -1, rounds = 0;
+        int rc = device_jp_coloring(h, h->lv[0].dA.ptr, h->lv[0].dA.idx, n, d_c8, &ncol, &rounds);
+        if (rc == GMG_OK && ncol >= 0) {
+            dev_pre.c8.resize((size_t)n);
+            rc = d2h(h, dev_pre.c8.data(), d_c8, (size_t)n);
+        }
+        if (rc != GMG_OK) {                  // the host colours: the stream must be usable for the rest of the set-up, or that fails with its own message
+            (void)hipStreamSynchronize(h->stream);
+            (void)hipGetLastError();
+            h->err.clear();
+            return GMG_OK;
+        }
+        h->timing["device_coloring_ms"] = ms_since(tc);
+        h->timing["device_coloring_rounds"] = rounds;
+        if (ncol < 0) return GMG_OK;
+        dev_pre.n_colors = ncol;
+        dev_pre.any_order = true;
+        colored_dev = true;
+        h->timing["colored_on_device"] = 1.0;
+        e.ahead.cancel();                    // (the greedy loop started ahead of the inspection colours for nobody)
+        mark("colored_on_device");
         return GMG_OK;
     }
     // A_1 .. A_L.  The device keeps A_k (Level::dA) and U_k (h->dU, h->dE3, built once per hierarchy) in natural numbering: inputs of the device
@@ -896,11 +936,12 @@ private:
             } else {
                 AheadColoring& ahead = e.ahead;
                 PreColoring* pre = nullptr;
-                if (!reorder0 && !base && mc && ahead.fut.valid() && ahead.ptr == colptr && !ahead.stop.load()) {
+                if (colored_dev) { ahead.cancel(); pre = &dev_pre; }      // the device's colours (color_level0_on_device): good for any visit order
+                else if (!reorder0 && !base && mc && ahead.fut.valid() && ahead.ptr == colptr && !ahead.stop.load()) {
                     ahead.pre.n_colors = ahead.fut.get();
                     if (ahead.pre.n_colors >= 0) pre = &ahead.pre;
                 } else ahead.cancel();
-                colored_ahead.store(pre ? 1 : 0);
+                colored_ahead.store(pre && !colored_dev ? 1 : 0);
                 lk.ord = make_ordering(PatternView{n, colptr, rowidx}, mc, h->cfg.row_align, h->cfg.sigma, reorder0 ? 1 : 0, base, /*idx_sorted=*/true, pre);   // the caller's arrays (canonical: checked / canonicalised at entry)
             }
         }
@@ -988,6 +1029,8 @@ private:
     bool ord_hit = false, blocked0 = false;
     bool reorder0 = false, permuted0 = false;      // level-0 locality renumbering (decided before level 0 is spawned)
     bool A0_uploaded = false;
+    bool colored_dev = false;         // level 0's colours came from the device (gmg_config::device_coloring), in dev_pre: set before level 0 is spawned
+    PreColoring dev_pre;
     std::vector<LevelStage> stage;
     std::vector<std::shared_future<void>> ord_done;
     std::vector<std::future<void>> op_done, tr_done;

@@ -220,8 +220,82 @@ inline int greedy_coloring_ahead(int n, const int* ptr, const int* idx, int64_t 
     }
     return ncol;
 }
-// a colouring made ahead of make_ordering (natural visit order): the bytes and the number of colours
-struct PreColoring { RawVec<unsigned char> c8; int n_colors = -1; };
+// a colouring made ahead of make_ordering: the bytes and the number of colours.  any_order: the colours do not depend on a visit order
+// (jp_coloring_host and its device twin), so they also serve a level whose rows follow a locality order; otherwise they are greedy colours
+// of the natural visit order and serve that order only
+struct PreColoring { RawVec<unsigned char> c8; int n_colors = -1; bool any_order = false; };
+
+// ---- Jones-Plassmann colouring in synchronous rounds (gmg_config::device_coloring): the SPECIFICATION of setup_kernels.hip.hpp::jp_round ----------
+// The greedy loops above are a chain through the whole graph; this colouring is a function of the pattern that many threads can evaluate at once:
+//   * priority of vertex v: the pair (mix32(v), v), compared lexicographically -- the hash makes the chains of descending priority short
+//     (O(log n / log log n) on bounded degree), the index makes the order total;
+//   * round r = 0, 1, ..: an uncoloured vertex WINS when its priority exceeds that of every neighbour that was uncoloured at the start of round r;
+//     a winner takes the smallest colour held by no neighbour coloured BEFORE round r (first fit);
+//   * two winners of a round are never adjacent (one of them would have lost to the other), so no winner's decision reads anything another
+//     winner of the round writes: the result depends on the pattern alone, not on threads, launch geometry or scheduling;
+//   * self-loops are ignored; duplicates do no harm; the pattern is symmetric, so CSC and CSR are the same thing.
+// mix32 (the "lowbias32" integer hash, public domain):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16   (mod 2^32)
+inline uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+// most colours of a byte colouring: 0 .. 253 (as in greedy_coloring_bytes; 255 is "none")
+constexpr int kJpMaxColors = 254;
+// First free colour given the coloured neighbours, 64 colours at a time: the mask of the window [base, base + 64) is collected over the row, the
+// first zero bit is the colour.  Window 0 decides nearly always; the later windows are the general path.  neighbour_colour(p): colour of the
+// row's p-th entry, or -1 when that entry does not count (self-loop, uncoloured).  Returns kJpMaxColors or more when 254 colours do not suffice.
+template <class F>
+inline int jp_first_fit(int p0, int p1, F neighbour_colour) {
+    for (int base = 0; base < 256; base += 64) {
+        uint64_t mask = 0;
+        for (int p = p0; p < p1; ++p) {
+            const int c = neighbour_colour(p);
+            if (c >= base && c < base + 64) mask |= (uint64_t)1 << (c - base);
+        }
+        if (~mask != 0) return base + __builtin_ctzll(~mask);
+    }
+    return 256;
+}
+// One byte per vertex; returns the number of colours, or -1 (c8 unusable) when more than 254 colours would be needed.  *rounds: the rounds it took
+// (0 with -1).  Sequential: a worklist of the uncoloured vertices, per round one pass that finds the winners and one that colours them.
+inline int jp_coloring_host(const PatternView& A, RawVec<unsigned char>& c8, int* rounds = nullptr) {
+    const int n = A.n_outer;
+    constexpr unsigned char kNone = 255;
+    c8.resize((size_t)std::max(n, 1));
+    std::memset(c8.data(), kNone, (size_t)std::max(n, 1));
+    unsigned char* cc = c8.data();
+    if (rounds) *rounds = 0;
+    std::vector<int> work((size_t)n), winners;
+    std::iota(work.begin(), work.end(), 0);
+    int ncol = 0, r = 0;
+    for (; !work.empty(); ++r) {
+        winners.clear();
+        size_t kept = 0;
+        for (const int v : work) {
+            const uint32_t pv = mix32((uint32_t)v);
+            bool win = true;
+            for (int p = A.ptr[v]; p < A.ptr[v + 1] && win; ++p) {
+                const int u = A.idx[p];
+                if (u == v || cc[u] != kNone) continue;
+                const uint32_t pu = mix32((uint32_t)u);
+                if (pu > pv || (pu == pv && u > v)) win = false;
+            }
+            if (win) winners.push_back(v); else work[kept++] = v;
+        }
+        work.resize(kept);
+        // (a winner's neighbours are no winners of this round: every colour read below was given before it)
+        for (const int v : winners) {
+            const int c = jp_first_fit(A.ptr[v], A.ptr[v + 1], [&](int p) { const int u = A.idx[p]; return (u == v || cc[u] == kNone) ? -1 : (int)cc[u]; });
+            if (c >= kJpMaxColors) return -1;
+            cc[v] = (unsigned char)c;
+            if (c >= ncol) ncol = c + 1;
+        }
+    }
+    if (rounds) *rounds = r;
+    return ncol;
+}
 
 // (Round 6 built the same colouring as a dataflow over strips of the visit sequence on several threads -- a vertex waits for the bytes of the
 // neighbours visited before it -- and removed it again: on a mesh in a local order the colouring is a chain along every mesh row, each row two
@@ -361,7 +435,9 @@ inline LevelOrdering make_ordering(const Mat& A, bool multicolor, int row_align,
     std::vector<int> color;
     RawVec<unsigned char> c8_own;
     const unsigned char* c8 = nullptr;
-    if (multicolor && pre && pre->n_colors >= 0 && base.empty() && pre->c8.n >= (size_t)n) {      // coloured ahead (greedy_coloring_ahead): the same bytes
+    // coloured ahead: greedy_coloring_ahead's bytes (the same as the loop below gives in natural order), or a colouring that depends on no visit
+    // order (PreColoring::any_order) -- the visit order `base` then still decides the sequence of the rows inside a class
+    if (multicolor && pre && pre->n_colors >= 0 && (base.empty() || pre->any_order) && pre->c8.n >= (size_t)n) {
         c8_own = std::move(pre->c8);
         o.n_colors = pre->n_colors;
         c8 = c8_own.data();

@@ -1047,4 +1047,109 @@ __global__ __launch_bounds__(kGershBlock) void gershgorin_reduce(const double* _
     }
 }
 
+// ---- colouring of level 0 on the device (gmg_config::device_coloring) ----------------------------------------------------------------
+// Jones-Plassmann in synchronous rounds, first fit: host_plan.hpp::jp_coloring_host is the specification, the bytes are the same bit for bit
+// (tests/test_gpu_device_coloring.py).  One launch of jp_round is one round; stream order separates the rounds, nothing waits for another
+// workgroup.  State of vertex v: st[v] = 0 while uncoloured, else (round + 1) << 8 | colour.  A vertex coloured in THIS round (stamp == round + 1)
+// looks uncoloured to every decision of the round, so the synchronous definition holds whatever order the waves run in: a thread that reads
+// st[u] while u's thread stores it sees 0 or this round's stamp -- the same thing (an aligned 32-bit word is stored whole).  Only v's thread
+// writes st[v] and c8[v].
+// ctl[0]: length of the worklist jp_compact builds; ctl[1]: rounds in which somebody won (every round with an uncoloured vertex has a winner:
+// the largest priority); ctl[2]: colours used; ctl[3]: a winner needed colour 254 or more.
+constexpr int kJpBlock = 256;
+constexpr int kJpMaxColors = 254;        // colours 0 .. 253 (host_plan.hpp::kJpMaxColors); byte 255 = none
+
+__device__ __forceinline__ unsigned jp_mix32(unsigned x) {      // host_plan.hpp::mix32
+    x ^= x >> 16; x *= 0x7feb352du;
+    x ^= x >> 15; x *= 0x846ca68bu;
+    x ^= x >> 16;
+    return x;
+}
+
+// list: the uncoloured vertices (null: all rows, the first rounds); count: its length; stamp: round + 1
+__global__ __launch_bounds__(kJpBlock) void jp_round(const int* __restrict__ ptr, const int* __restrict__ idx, int n, const int* __restrict__ list, int count,
+                                                     unsigned stamp, unsigned* st, unsigned char* c8, unsigned* ctl) {
+    const int i = blockIdx.x * kJpBlock + threadIdx.x;
+    int colour = -1;                     // >= 0: this thread's vertex won and took it
+    bool overflow = false;
+    if (i < count) {
+        const int v = list ? list[i] : i;
+        if (st[v] == 0) {
+            const unsigned pv = jp_mix32((unsigned)v);
+            const int p0 = ptr[v], p1 = ptr[v + 1];
+            bool win = true;
+            unsigned long long mask = 0;                // colours 0 .. 63 of the neighbours coloured before this round
+            for (int p = p0; p < p1; ++p) {
+                const int u = idx[p];
+                if (u == v || (unsigned)u >= (unsigned)n) continue;
+                const unsigned su = st[u];
+                if (su == 0 || (su >> 8) == stamp) {    // uncoloured at the start of this round
+                    const unsigned pu = jp_mix32((unsigned)u);
+                    if (pu > pv || (pu == pv && u > v)) { win = false; break; }
+                } else if ((su & 255u) < 64u) mask |= 1ull << (su & 255u);
+            }
+            if (win) {
+                int c;
+                if (~mask != 0) c = __ffsll((long long)~mask) - 1;
+                else {
+                    // the general path: 64 colours at a time, as jp_first_fit does (every neighbour that counts is coloured: a winner has no
+                    // uncoloured neighbour of higher priority, and those of lower priority hold no colour)
+                    c = 256;
+                    for (int base = 64; base < 256 && c == 256; base += 64) {
+                        unsigned long long m = 0;
+                        for (int p = p0; p < p1; ++p) {
+                            const int u = idx[p];
+                            if (u == v || (unsigned)u >= (unsigned)n) continue;
+                            const unsigned su = st[u];
+                            if (su == 0 || (su >> 8) == stamp) continue;
+                            const int cu = (int)(su & 255u) - base;
+                            if (cu >= 0 && cu < 64) m |= 1ull << cu;
+                        }
+                        if (~m != 0) c = base + __ffsll((long long)~m) - 1;
+                    }
+                }
+                if (c >= kJpMaxColors) overflow = true;
+                else {
+                    colour = c;
+                    st[v] = stamp << 8 | (unsigned)c;
+                    c8[v] = (unsigned char)c;
+                }
+            }
+        }
+    }
+    // per wave: did anybody win, and the largest colour taken; the counters only grow, so a wave that reads them large enough adds nothing
+    int top = colour;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) top = max(top, __shfl_xor(top, off, 64));
+    const bool any_overflow = __any(overflow);
+    if ((threadIdx.x & 63) == 0) {
+        if (top >= 0) {
+            if (ctl[1] < stamp) atomicMax(&ctl[1], stamp);
+            if (ctl[2] < (unsigned)top + 1u) atomicMax(&ctl[2], (unsigned)top + 1u);
+        }
+        if (any_overflow) atomicMax(&ctl[3], 1u);
+    }
+}
+
+// The vertices of `src` (null: all rows) that are still uncoloured, appended to dst in no particular order (the order decides no colour);
+// ctl[0] (zeroed by the caller) counts them: one atomic add per workgroup.
+__global__ __launch_bounds__(kJpBlock) void jp_compact(const int* __restrict__ src, int count, const unsigned* __restrict__ st, int* __restrict__ dst, unsigned* ctl) {
+    __shared__ unsigned wave_at[kJpBlock / 64 + 1];
+    const int i = blockIdx.x * kJpBlock + threadIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int v = -1;
+    if (i < count) { v = src ? src[i] : i; if (st[v] != 0) v = -1; }
+    const unsigned long long live = __ballot(v >= 0);
+    const int before = __popcll(live & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_at[wave] = (unsigned)__popcll(live);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned total = 0;
+        for (int w = 0; w < kJpBlock / 64; ++w) { const unsigned c = wave_at[w]; wave_at[w] = total; total += c; }
+        wave_at[kJpBlock / 64] = total ? atomicAdd(&ctl[0], total) : 0u;
+    }
+    __syncthreads();
+    if (v >= 0) dst[wave_at[kJpBlock / 64] + wave_at[wave] + (unsigned)before] = v;
+}
+
 }  // namespace gmgs

@@ -161,6 +161,14 @@ typedef struct {
                               last; otherwise, and with 0, the head is the first colour launch.  Timing key "heads_folded" counts the folded heads
                               ("heads_enqueued" counts every launch enqueued ahead of the decision, folded or not).  Added after accelerate, in front of which
                               it stands: accelerate stays the last field, and a binding built against another edition is refused by gmg_config_size */
+    int device_coloring;   /* 0 (default): level 0 is coloured by the host's sequential greedy loop.  1: a gmg_set_system that needs a new ordering of level 0 (no
+                              ordering-cache hit, no values-only refresh), on a colour-major level 0 with the multicolour smoother, device_setup = 1 and
+                              device_rap = 1, takes the colour bytes from the device: Jones-Plassmann rounds with first-fit colours on the uploaded pattern
+                              (DESIGN.md "Colouring level 0 on the device"), a pure function of the pattern.  It is ANOTHER colouring than the greedy one,
+                              hence another Gauss-Seidel ordering: colour counts and cycle counts may differ.  Where the preconditions fail, 254 colours do
+                              not suffice or the device colouring fails, the host colours and the results are those of 0.  Timing keys "colored_on_device"
+                              (0 / 1), "device_coloring_ms", "device_coloring_rounds".  Values other than 0 / 1: GMG_ERR_INVALID.  In front of accelerate,
+                              like fold_head */
     int accelerate;        /* 0 (default): the solve loop as in the reference (cycle, residual check, repeat).  m in 1..4: gmg_solve, gmg_solve_x0_rhs and
                               gmg_solve_device recombine the iterates by truncated GCR with the V-cycle as the preconditioner: every cycle's step is
                               orthogonalised (in the stop type's weighted inner product, per right-hand-side column) against the last m - 1 stored

@@ -131,6 +131,14 @@ int gmg_host_plan_level(int n, const int* colptr, const int* rowidx, const doubl
  * the solver takes: the block sweep is a regular splitting).  reason (optional): 0 chosen, 1 rows too short, 2 signs. */
 int gmg_host_fine_block_rule(int n, const int* colptr, const int* rowidx, const double* val, int* blocked, int* reason);
 
+/* The colouring behind gmg_config::device_coloring on a caller's symmetric pattern (n >= 1; CSC or CSR, the same thing; self-loops ignored):
+ * Jones-Plassmann in synchronous rounds with first-fit colours (csrc/host_plan.hpp::jp_coloring_host, the specification) and the device kernels
+ * that must give the same bytes (csrc/setup_kernels.hip.hpp::jp_round; the handle lends its stream and pool; the pattern is uploaded, the bytes
+ * copied back).  colours: n bytes; *n_colors: colours used, or -1 when 254 do not suffice (colours then mean nothing, *rounds = 0); *rounds:
+ * rounds until no vertex was left.  GMG_ERR_INVALID for arrays that would take a reader out of bounds; the host entry needs no device. */
+int gmg_jp_coloring_host(int n, const int* colptr, const int* rowidx, unsigned char* colours, int* n_colors, int* rounds);
+int gmg_jp_coloring_device(gmg_handle h, int n, const int* colptr, const int* rowidx, unsigned char* colours, int* n_colors, int* rounds);
+
 /* ---- measurement ---------------------------------------------------------------------------- */
 /* Average duration (ms) of one unit of level-k work, measured with HIP events on the engine stream:
  * kind 0 = full smoothing sweep (all colours), 1 = residual r=b-Ax, 2 = restrict, 3 = prolong_add,
