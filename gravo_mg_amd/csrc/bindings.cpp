@@ -339,6 +339,7 @@ public:
         else if (key == "accelerate") c.accelerate = (int)value;
         else if (key == "fold_head") c.fold_head = (int)value;
         else if (key == "device_coloring") c.device_coloring = (int)value;
+        else if (key == "pcg") c.pcg = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

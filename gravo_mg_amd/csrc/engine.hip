@@ -49,6 +49,7 @@
 #include "setup_kernels.hip.hpp"
 #include "hierarchy_kernels.hip.hpp"
 #include "accel_kernels.hip.hpp"
+#include "pcg_kernels.hip.hpp"
 
 using namespace gmg;
 using clk = std::chrono::steady_clock;
@@ -140,6 +141,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->fold_head = 1;
     cfg->uniform_slices = 1;
     cfg->color_ahead = 1;
+    cfg->pcg = 0;             // the plain solve loop (1: conjugate gradients preconditioned by a symmetric cycle, solve_common)
     cfg->device_coloring = 0; // level 0 is coloured by the host's greedy loop (1: Jones-Plassmann rounds on the device, another colouring: see gmg_config)
     cfg->dist_exchange = 0;
     cfg->block_fine = 1;      // level 0 blocked too where it pays and is safe (long rows, Stieltjes matrix): see gmg_config
@@ -158,8 +160,13 @@ int gmg_device_count(void) try {
     return n;
 } GMG_CATCH_0
 
+// Why this thread's last gmg_create refused a configuration, where it says so: there is no handle to ask, gmg_last_error(NULL) returns it
+static std::string& create_error() { static thread_local std::string s; return s; }
+static int create_refused(int code, const char* why) { create_error() = why; return code; }
+
 int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     if (!out) return GMG_ERR_INVALID;
+    create_error().clear();
     gmg_config c;
     if (cfg) c = *cfg; else gmg_config_default(&c);
     if (c.sigma < 0 || c.sigma % 64 || c.restrict_sigma < 0 || c.restrict_sigma % 64 || c.row_align <= 0 || c.row_align % 64 || c.pre_iters < 0 || c.post_iters < 0 ||
@@ -169,6 +176,14 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     if (c.device_coloring < 0 || c.device_coloring > 1) return GMG_ERR_INVALID;
     if (c.smoother < GMG_SMOOTHER_MULTICOLOR_GS || c.smoother > GMG_SMOOTHER_CHEBYSHEV) return GMG_ERR_INVALID;
     if (c.accelerate > 0 && c.inner_precision) return GMG_ERR_UNSUPPORTED;      // the recombination is fp64 only (gmg_config::accelerate)
+    if (c.pcg < 0 || c.pcg > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::pcg must be 0 or 1");
+    if (c.pcg) {        // conjugate gradients need a symmetric positive definite preconditioner: a pointwise smoother, as many steps down as up (gmg_config::pcg)
+        if (c.smoother != GMG_SMOOTHER_CHEBYSHEV && c.smoother != GMG_SMOOTHER_JACOBI)
+            return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg needs a pointwise smoother (GMG_SMOOTHER_CHEBYSHEV or GMG_SMOOTHER_JACOBI): a Gauss-Seidel cycle is not a symmetric operator");
+        if (c.pre_iters != c.post_iters || c.pre_iters < 1) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg needs pre_iters == post_iters >= 1: the cycle must be a symmetric operator");
+        if (c.accelerate != 0) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg and gmg_config::accelerate are two solve loops: set one of them");
+        if (c.inner_precision != 0) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg is fp64 only (inner_precision = 0)");
+    }
     gmg_handle h = new gmg_solver_s();
     h->cfg = c;
     if (h->cfg.host_threads <= 0) h->cfg.host_threads = hw_threads();
@@ -219,7 +234,7 @@ void gmg_destroy(gmg_handle h) {
     delete h;
 }
 
-const char* gmg_last_error(gmg_handle h) { return h ? h->err.c_str() : "null handle"; }
+const char* gmg_last_error(gmg_handle h) { return h ? h->err.c_str() : (create_error().empty() ? "null handle" : create_error().c_str()); }
 
 int gmg_set_num_levels(gmg_handle h, int L) try {
     if (!h || L < 0 || L > 64) return h ? fail(h, GMG_ERR_INVALID, "invalid level count") : GMG_ERR_INVALID;
@@ -859,11 +874,40 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         if (rule_goes_on(rule_after(rule, residue))) launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
         return GMG_OK;
     };
+    // gmg_config::pcg = 1: conjugate gradients with the cycle as the preconditioner (launch_pcg_step).  The cycle runs on the CG
+    // residual from a zero guess, so for the duration of the loop level 0's x / b are z / r and the CG iterate and the true right-hand side live in
+    // the PCG state (pcg_exchange); the confirming check -- as in the accelerated branch -- and the caller's fetch() see them exchanged back.
+    const int pcg = h->cfg.pcg;
+    int pcg_confirmations = 0;
+    bool pcg_first = true, pcg_fresh = false;
+    struct PcgRestore { gmg_handle h; ~PcgRestore() { if (h->pcg.exchanged) pcg_exchange(h); } } pcg_restore{h};        // (every way out, errors included)
+    auto pcg_step = [&](SolveRule& rule, double& residue, int&) -> int {
+        if ((rc = vcycle_legs<double>(h, d, -1, kPcgGraphSalt, 0, nullptr))) return rc;          // z = cycle(rhs = r, x = 0)
+        if ((rc = launch_pcg_step(h, d, stop_type, pcg_first, pcg_fresh))) return rc;
+        pcg_first = pcg_fresh = false;
+        if ((rc = wait_norm(h))) return rc;
+        residue = norm_from_sums(h->h_norm, d, stop_type);
+        if (rule_goes_on(rule_after(rule, residue))) return GMG_OK;
+        const double recurrence = residue;
+        pcg_exchange(h);                                                          // level 0 holds the iterate and the true right-hand side
+        if ((rc = launch_norm(h, d, stop_type))) return rc;                       // it would end the loop: the check on the iterate itself decides
+        if ((rc = wait_norm(h))) return rc;
+        residue = norm_from_sums(h->h_norm, d, stop_type);
+        ++pcg_confirmations;
+        rule = rule_confirmed(rule, recurrence, residue, rule_floor(h->h_norm, d, stop_type));
+        // (confirmed, above the tolerance and the loop will go on: r is recomputed from the iterate, the next step starts a new recurrence)
+        if (rule_goes_on(rule_after(rule, residue))) {
+            launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->pcg.b);
+            pcg_exchange(h);
+            pcg_fresh = true;
+        }
+        return GMG_OK;
+    };
     // Head of the next cycle (gmg_config::speculate_head): the check's reduction takes the loop's decision on the device too (same sums, same
     // functions: gmgk::reduce_partials / SolveWatch, solve_rule.hpp) and the first colour launch of the next cycle is enqueued behind it at
     // once -- it returns without touching x when the iteration has stopped.  The ~6 us the host needs to see the norm and to get a launch to
     // the device are hidden behind that launch.  The loop follows the device's word.
-    const bool heads = loop_enqueues_heads(h, d, accel == 0);
+    const bool heads = loop_enqueues_heads(h, d, accel == 0 && pcg == 0);
     CycleWatch watch{1, tol, stop_type, 0};
     // gmg_config::fold_head: the check computes the head's values too and the launch enqueued behind it is the second colour launch, which
     // commits them (engine_cycle.hip.hpp::fold_eligible) -- a stopped iteration still returns at once, x the iterate that was checked.
@@ -887,9 +931,26 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         HIPCHK(hipMemcpyAsync(h->accel.xk, l0.x, sizeof(double) * (size_t)l0.n_pad * d, hipMemcpyDeviceToDevice, h->stream));
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->accel.r);
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, accel_step);
+    } else if (pcg) {
+        if ((rc = ensure_pcg(h))) return rc;
+        HIPCHK(hipMemsetAsync(h->pcg.scal, 0, sizeof(double) * ((size_t)4 * h->pcg.d + 2), h->stream));
+        launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->pcg.b);                  // r = b - A x0
+        HIPCHK(hipMemsetAsync(h->pcg.x, 0, sizeof(double) * (size_t)l0.n_pad * d, h->stream));      // the first cycle's zero guess (later ones: pcg_direction)
+        pcg_exchange(h);
+        verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, pcg_step);
     } else
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, plain_step);
     if (verdict < 0) return verdict;
+    if (h->pcg.exchanged) return fail(h, GMG_ERR_STATE, "the preconditioned CG loop ended without its confirming check");      // (cannot happen: solve_loop ends where the step confirmed)
+    h->timing["pcg"] = pcg;
+    h->timing["pcg_confirmations"] = pcg_confirmations;
+    double pcg_counts[2] = {0.0, 0.0};
+    if (pcg) {
+        HIPCHK(hipMemcpyAsync(pcg_counts, h->pcg.scal + (size_t)4 * h->pcg.d, sizeof(pcg_counts), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
+    h->timing["pcg_guard_steps"] = pcg_counts[0];
+    h->timing["pcg_restarts"] = pcg_counts[1];
     h->timing["accelerate"] = accel;
     h->timing["accel_confirmations"] = confirmations;
     double guard_steps = 0.0;

@@ -580,6 +580,7 @@ int ensure_vectors(gmg_handle h, int d) {
     drop_graphs(h);
     unbind_level0(h);
     h->accel = {};
+    h->pcg = {};
     // a zeroed n_pad x d vector of the level, or none (wanted = false): the old one goes back to the pool either way
     auto vec = [&](auto& v, const Level& l, bool wanted) -> int {
         v.reset();
@@ -1193,6 +1194,71 @@ int launch_accel_step(gmg_handle h, int d, int type, int done) {
                                           zw ? zw : a.z0 + off, qw ? qw : q0, a.z0 + off, q0, alpha + c0, guarded + c0, l.b + off, w, ld, n_pairs, a.partials));
         // (the floor guard's <b, b>: kept from the first update's sums, zero until then)
         if (done == 0) hipLaunchKernelGGL(gmgk::accel_reduce_bb, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, bb + c0);
+        launch_reduce(h, nblk, dc, c0, c0 + 4 >= d, a.partials);
+    });
+    if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
+    return GMG_OK;
+}
+
+// ---- preconditioned CG solve loop (gmg_config::pcg; engine.hip::solve_common; kernels: pcg_kernels.hip.hpp) --------------------------
+
+// Graphs of the cycle captured while the owners are exchanged hold the exchanged buffers: a key of their own (vcycle_legs' key_salt).  The two
+// states hand lv[0].x / lv[0].b the same two pairs of buffers for as long as the level vectors live (every solve exchanges an even number of times).
+constexpr int kPcgGraphSalt = 200000;
+
+// its vectors and scalars, for the level vectors as they are now (n_pad x dcap)
+int ensure_pcg(gmg_handle h) {
+    auto& a = h->pcg;
+    const int n_pad = h->lv[0].n_pad, D = h->dcap;
+    if (a.x && a.d == D && a.n_pad == n_pad) return GMG_OK;
+    a = {};
+    const size_t count = (size_t)n_pad * D;
+    int rc;
+    for (DevBuf<double>* p : {&a.x, &a.b, &a.p}) {
+        if ((rc = dev_alloc(h, *p, count))) return rc;
+        HIPCHK(hipMemsetAsync(*p, 0, sizeof(double) * count, h->stream));          // (padding rows: zero, and no kernel writes anything else there)
+    }
+    if ((rc = dev_alloc(h, a.scal, (size_t)4 * D + 2)) || (rc = dev_alloc(h, a.partials, (size_t)gmgk::kAccelMaxBlocks * 8))) return rc;
+    a.d = D; a.n_pad = n_pad;
+    return GMG_OK;
+}
+
+// lv[0].x <-> pcg.x, lv[0].b <-> pcg.b: who owns the CG iterate and the true right-hand side (gmg_solver_s::PcgState)
+void pcg_exchange(gmg_handle h) {
+    Level& l = h->lv[0];
+    std::swap(l.x, h->pcg.x);
+    std::swap(l.b, h->pcg.b);
+    h->pcg.exchanged = !h->pcg.exchanged;
+}
+
+// One CG step behind the cycle, owners exchanged: lv[0].b holds r, lv[0].x holds z = cycle(r, 0), pcg.x the iterate, pcg.b the true b.
+// first: the first iteration of the solve; fresh: r was recomputed from the iterate.  Leaves the new iterate in pcg.x, the recurrence residual
+// in lv[0].b, zeros in lv[0].x and the check's sums on their way to h_norm (wait_norm).
+int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
+    auto& a = h->pcg;
+    Level& l = h->lv[0];
+    const int DA = a.d, ld = l.n_pad, n_pairs = l.n_pad / 2;
+    const int nblk = std::max(1, std::min(gmgk::kAccelMaxBlocks, (n_pairs + gmgk::kAccelBlock - 1) / gmgk::kAccelBlock));
+    const double* w = type == 1 ? h->d_minv : (type == 2 ? h->d_mass : nullptr);
+    double *rho = a.scal, *beta = a.scal + DA, *alpha = a.scal + 2 * DA, *restart = a.scal + 3 * DA, *guard_steps = a.scal + 4 * DA, *restarts = a.scal + 4 * DA + 1;
+    // the check's sums of the last update or confirmation, where the device reads them (launch_reduce)
+    const double* sums = first ? nullptr : (polled(h) ? h->h_norm : h->d_norm.get());
+    double *r = l.b, *z = l.x, *q = l.r;
+    for_col_chunks(d, [&](int c0, int dc) {
+        const size_t off = (size_t)c0 * ld;
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, r + off, z + off, ld, n_pairs, a.partials));
+        hipLaunchKernelGGL(gmgk::pcg_reduce_beta, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, rho + c0, beta + c0, restart + c0,
+                           (int)first, (int)fresh, restarts);
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_direction<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, z + off, a.p + off, beta + c0, ld, n_pairs));
+    });
+    launch_spmv<double>(h, l, d, 0, nullptr, a.p.get(), q);
+    for_col_chunks(d, [&](int c0, int dc) {
+        const size_t off = (size_t)c0 * ld;
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.p + off, q + off, ld, n_pairs, a.partials));
+        hipLaunchKernelGGL(gmgk::pcg_reduce_alpha, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, rho + c0, alpha + c0, restart + c0,
+                           sums ? sums + 2 * c0 : nullptr, guard_steps);
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_update<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.x + off, r + off, a.p + off, q + off, alpha + c0,
+                                          a.b + off, w, ld, n_pairs, a.partials));
         launch_reduce(h, nblk, dc, c0, c0 + 4 >= d, a.partials);
     });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));

@@ -257,6 +257,19 @@ struct gmg_solver_s {
         DevBuf<double> partials;         // kAccelMaxBlocks x kAccelMaxComp
         int depth = 0, d = 0, n_pad = 0;
     } accel;
+    // The preconditioned CG solve loop (gmg_config::pcg = 1; engine.hip::solve_common): three level-0 vectors (n_pad x d) from the pool, the
+    // device-side scalars and the partial sums of its kernels.  Allocated by the first PCG solve (ensure_pcg), released with the level vectors
+    // (pcg = {}: ensure_vectors, drop_system).  WHILE THE LOOP RUNS the cycle's right-hand side lv[0].b is the CG residual r and its iterate
+    // lv[0].x the preconditioned residual z, so x and b below own the CG iterate and the true right-hand side; the owners are exchanged
+    // (pcg_exchange, `exchanged` says which way round they are) for the confirming check and before the solve returns: outside solve_common
+    // lv[0].x / lv[0].b are what they are on every handle, and x / b here two spare buffers.  q = A p lives in lv[0].r.
+    struct PcgState {
+        DevBuf<double> x, b, p;
+        DevBuf<double> scal;             // rho[d], beta[d], alpha[d], restart[d] (1: the column took a guard, its next iteration is fresh), guarded steps, restarts: 4 d + 2 doubles
+        DevBuf<double> partials;         // kAccelMaxBlocks x 8
+        int d = 0, n_pad = 0;
+        bool exchanged = false;
+    } pcg;
     // Head of the next cycle (gmg_config::speculate_head; engine.hip::solve_common): the solve loop's decision is taken by the check's
     // reduction on the device (d_watch: {double least; int go}), the first colour launch of the next cycle is enqueued behind it before the
     // host has seen the norm, and returns at once when the iteration stopped.  Only the device words live here: what the reduction needs to
@@ -570,6 +583,7 @@ void drop_system(gmg_handle h) {
     drop_graphs(h);
     unbind_level0(h);
     h->accel = {};
+    h->pcg = {};
     h->dist_ready = false;
     h->lv.clear();
     h->dcap = 0;

@@ -305,7 +305,9 @@ class MultigridSolver(object):
         3 the packed lower triangle of that inverse, applied on the device at any size: half the resident bytes and half the bytes per application against a second,
         small reduction launch -- GMG_COARSE_DEVICE_TRIANGLE), use_graph, block_rows, block_from_level, device,
         accelerate (0 = default: the reference's solve loop; m in 1..4: truncated GCR around the V-cycle -- each cycle's step is orthogonalised against the last m - 1 and scaled so
-        that the tested residue is minimal and cannot grow; fp64 and one device only, gmg_config::accelerate)."""
+        that the tested residue is minimal and cannot grow; fp64 and one device only, gmg_config::accelerate),
+        pcg (0 = default; 1: conjugate gradients preconditioned by the V-cycle -- needs smoother 1 or 2 and equal pre / post iteration counts, which make the cycle a symmetric
+        positive definite operator; converges for every symmetric positive definite system; not together with accelerate, fp64 and one device only, gmg_config::pcg)."""
         self.solver.set_engine_option(str(key), float(value))
         if str(key) == "device":
             self._device = int(value)

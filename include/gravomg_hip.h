@@ -161,6 +161,26 @@ typedef struct {
                               last; otherwise, and with 0, the head is the first colour launch.  Timing key "heads_folded" counts the folded heads
                               ("heads_enqueued" counts every launch enqueued ahead of the decision, folded or not).  Added after accelerate, in front of which
                               it stands: accelerate stays the last field, and a binding built against another edition is refused by gmg_config_size */
+    int pcg;               /* 0 (default): the solve loop as in the reference.  1: gmg_solve, gmg_solve_x0_rhs and gmg_solve_device run preconditioned
+                              conjugate gradients with the handle's V-cycle as the preconditioner, per right-hand-side column:
+                                r = b - A x0;  repeat:  z = cycle(rhs = r, x = 0);  rho = <r, z>;  beta = rho / rho_prev (0 in a fresh recurrence);
+                                p = z + beta p;  q = A p;  alpha = rho / <p, q>;  x += alpha p;  r -= alpha q;  residue from sum w r^2 / sum w b^2
+                              (<.,.> plain sums over the rows; w the stop type's weights).  CG needs a symmetric positive definite preconditioner, which a
+                              cycle with a pointwise smoother (GMG_SMOOTHER_CHEBYSHEV, GMG_SMOOTHER_JACOBI), Galerkin levels, an exact coarsest solve
+                              and pre_iters == post_iters >= 1 is: any other smoother or sweep counts, accelerate != 0 or inner_precision != 0 make
+                              gmg_create return GMG_ERR_UNSUPPORTED, values other than 0 / 1 GMG_ERR_INVALID (gmg_last_error(NULL) then says which, for
+                              the calling thread's last gmg_create).  As with accelerate, the residue comes out of a recurrence and one that would end the
+                              loop is confirmed by the ordinary residual check on the iterate the caller gets (that value is reported); where the loop
+                              goes on, r is recomputed from the iterate and the next iteration starts a fresh recurrence.  Guards, decided on the device:
+                              a column whose <p, q> is not positive or not finite, whose rho is not finite, or whose sum w r^2 is at most 1e-25 sum w b^2
+                              (the accuracy floor, as in accelerate) takes alpha = 0 in that iteration and a fresh recurrence in the next.  Three more
+                              level-0 vectors on the device (the iterate, the right-hand side, p; q uses level 0's residual vector), allocated by the first
+                              such solve.  One device only (the multi-rank entry points refuse pointwise smoothers).  Unchanged by this field:
+                              gmg_run_cycles, gmg_vcycle, gmg_profile_cycle and the operator entry points.  Every solve writes the timing keys "pcg"
+                              (0 / 1), "pcg_confirmations", "pcg_guard_steps" (columns x iterations that took a guard) and "pcg_restarts" (columns x
+                              iterations after the first that started a fresh recurrence) -- with pcg = 0 too, as zeros: the only trace of this field on
+                              the default path.  Added after device_coloring, in front of which it stands: accelerate
+                              stays the last field, and a binding built against another edition is refused by gmg_config_size */
     int device_coloring;   /* 0 (default): level 0 is coloured by the host's sequential greedy loop.  1: a gmg_set_system that needs a new ordering of level 0 (no
                               ordering-cache hit, no values-only refresh), on a colour-major level 0 with the multicolour smoother, device_setup = 1 and
                               device_rap = 1, takes the colour bytes from the device: Jones-Plassmann rounds with first-fit colours on the uploaded pattern
@@ -192,6 +212,7 @@ int gmg_config_size(void);
  * (gravomg_bindings/src/cpp/core.cpp:27,138). */
 int gmg_create(const gmg_config* cfg, gmg_handle* out);
 void gmg_destroy(gmg_handle h);
+/* h = NULL: why the calling thread's last gmg_create refused its configuration, where it says so (gmg_config::pcg); "null handle" otherwise */
 const char* gmg_last_error(gmg_handle h);
 /* Number of usable HIP devices (0 on a CPU-only box); never fails. */
 /* Host threads a handle uses unless gmg_config::host_threads says otherwise: the CPUs this PROCESS may use (hardware threads,
