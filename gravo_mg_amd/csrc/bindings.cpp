@@ -340,6 +340,8 @@ public:
         else if (key == "fold_head") c.fold_head = (int)value;
         else if (key == "device_coloring") c.device_coloring = (int)value;
         else if (key == "pcg") c.pcg = (int)value;
+        else if (key == "reorder_pointwise") c.reorder_pointwise = (int)value;
+        else if (key == "zero_guess_step") c.zero_guess_step = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

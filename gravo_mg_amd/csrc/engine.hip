@@ -141,6 +141,8 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->fold_head = 1;
     cfg->uniform_slices = 1;
     cfg->color_ahead = 1;
+    cfg->reorder_pointwise = 0; // a pointwise smoother keeps the caller's numbering of level 0 (1: reorder_fine applies to it too, see gmg_config)
+    cfg->zero_guess_step = 0; // a pointwise smoother reads a materialised zero guess (1: its first step is c * b / diag, see gmg_config)
     cfg->pcg = 0;             // the plain solve loop (1: conjugate gradients preconditioned by a symmetric cycle, solve_common)
     cfg->device_coloring = 0; // level 0 is coloured by the host's greedy loop (1: Jones-Plassmann rounds on the device, another colouring: see gmg_config)
     cfg->dist_exchange = 0;
@@ -176,6 +178,8 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     if (c.device_coloring < 0 || c.device_coloring > 1) return GMG_ERR_INVALID;
     if (c.smoother < GMG_SMOOTHER_MULTICOLOR_GS || c.smoother > GMG_SMOOTHER_CHEBYSHEV) return GMG_ERR_INVALID;
     if (c.accelerate > 0 && c.inner_precision) return GMG_ERR_UNSUPPORTED;      // the recombination is fp64 only (gmg_config::accelerate)
+    if (c.reorder_pointwise < 0 || c.reorder_pointwise > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::reorder_pointwise must be 0 or 1");
+    if (c.zero_guess_step < 0 || c.zero_guess_step > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::zero_guess_step must be 0 or 1");
     if (c.pcg < 0 || c.pcg > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::pcg must be 0 or 1");
     if (c.pcg) {        // conjugate gradients need a symmetric positive definite preconditioner: a pointwise smoother, as many steps down as up (gmg_config::pcg)
         if (c.smoother != GMG_SMOOTHER_CHEBYSHEV && c.smoother != GMG_SMOOTHER_JACOBI)
@@ -450,6 +454,8 @@ int gmg_get_timing(gmg_handle h, const char* key, double* out) try {
     if (!h || !key || !out) return GMG_ERR_INVALID;
     if (std::string(key) == "device_bytes_now") { *out = (double)h->pool.live_bytes; return GMG_OK; }      // device memory the handle holds at this moment (pool blocks in use)
     if (std::string(key) == "device_blocks_now") { *out = (double)(h->pool.size_of.size() - h->pool.parked.size()); return GMG_OK; }      // ... and how many blocks that is
+    if (std::string(key) == "zero_guess_steps") { *out = (double)h->zero_steps; return GMG_OK; }                   // zero-step launches enqueued so far (gmg_config::zero_guess_step)
+    if (std::string(key) == "restrict_steps_fused") { *out = (double)h->fused_step_restrictions; return GMG_OK; }  // ... and restrictions that computed the step instead
     if (std::string(key) == "restrict_sweeps_fused") { *out = (double)h->fused_restrictions; return GMG_OK; }      // fused restriction + first pre-sweep launches enqueued so far (gmg_config::fuse_restrict_sweep)
     auto it = h->timing.find(key);
     if (it == h->timing.end()) return fail(h, GMG_ERR_INVALID, std::string("unknown timing key: ") + key);
@@ -484,7 +490,8 @@ int gmg_smooth_residual(gmg_handle h, int k, const double* b, double* x, int d, 
     Level& l = h->lv[k];
     if ((rc = to_device(h, k, b, d, l.b))) return rc;
     SmoothAsk<double> ask;                         // (a single level's sweeps: nothing ran ahead of them, nothing rides on them)
-    ask.from_zero = from_zero != 0 && k > 0 && smooth_from_zero_ok(h, l, iters);
+    // (a pointwise smoother's zero step serves level 0 as well: where the engine supplies the zero guess, the cycle uses it there)
+    ask.from_zero = from_zero != 0 && (k > 0 || pointwise_smoother(h->cfg)) && smooth_from_zero_ok(h, l, iters);
     if (from_zero) HIPCHK(hipMemsetAsync(l.x, 0, sizeof(double) * (size_t)l.n_pad * d, h->stream));
     else if ((rc = to_device(h, k, x, d, l.x))) return rc;
     const SmoothDone<double> swept = launch_smooth<double>(h, l, d, iters, ask);
@@ -603,7 +610,7 @@ int f32_out(gmg_handle h, int k, const float* v32, double* v64, int d, double* d
 void f32_smooth_residual(gmg_handle h, int k, int d, int iters, bool from_zero, bool first_done) {
     Level& l = h->lv[k];
     SmoothAsk<float> ask;
-    ask.from_zero = from_zero && k > 0 && smooth_from_zero_ok(h, l, iters);
+    ask.from_zero = from_zero && (k > 0 || pointwise_smoother(h->cfg)) && smooth_from_zero_ok(h, l, iters);
     ask.first_done = first_done;
     if (from_zero && !ask.from_zero) (void)hipMemsetAsync(l.x32, 0, sizeof(float) * (size_t)l.n_pad * d, h->stream);
     const SmoothDone<float> swept = launch_smooth<float>(h, l, d, iters, ask);
@@ -882,7 +889,8 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     bool pcg_first = true, pcg_fresh = false;
     struct PcgRestore { gmg_handle h; ~PcgRestore() { if (h->pcg.exchanged) pcg_exchange(h); } } pcg_restore{h};        // (every way out, errors included)
     auto pcg_step = [&](SolveRule& rule, double& residue, int&) -> int {
-        if ((rc = vcycle_legs<double>(h, d, -1, kPcgGraphSalt, 0, nullptr))) return rc;          // z = cycle(rhs = r, x = 0)
+        // z = cycle(rhs = r, x = 0); with gmg_config::zero_guess_step the cycle knows that its guess is zero and nobody writes the zeros
+        if ((rc = vcycle_legs<double>(h, d, -1, kPcgGraphSalt, 0, nullptr, /*zero_guess*/ true))) return rc;
         if ((rc = launch_pcg_step(h, d, stop_type, pcg_first, pcg_fresh))) return rc;
         pcg_first = pcg_fresh = false;
         if ((rc = wait_norm(h))) return rc;
@@ -935,7 +943,8 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         if ((rc = ensure_pcg(h))) return rc;
         HIPCHK(hipMemsetAsync(h->pcg.scal, 0, sizeof(double) * ((size_t)4 * h->pcg.d + 2), h->stream));
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->pcg.b);                  // r = b - A x0
-        HIPCHK(hipMemsetAsync(h->pcg.x, 0, sizeof(double) * (size_t)l0.n_pad * d, h->stream));      // the first cycle's zero guess (later ones: pcg_direction)
+        // the first cycle's zero guess (later ones: pcg_direction) -- unless the cycle starts from zero by itself (level0_zero_guess)
+        if (!level0_zero_guess(h)) HIPCHK(hipMemsetAsync(h->pcg.x, 0, sizeof(double) * (size_t)l0.n_pad * d, h->stream));
         pcg_exchange(h);
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, pcg_step);
     } else

@@ -215,12 +215,42 @@ SmoothDone<T> launch_gs_sweeps(gmg_handle h, Level& l, int d, int iters, const S
     return done;
 }
 
+// The factor of a pointwise smoother's first step on a zero iterate, x = c * (b / diag) (gmgk::zero_step_row): Jacobi's damping, or the second
+// coefficient of Chebyshev step 0 on this level (its first multiplies a p that does not exist yet).
 template <class T>
-void launch_jacobi_sweeps(gmg_handle h, Level& l, int d, int iters) {
+T zero_step_coeff(gmg_handle h, const Level& l) {
+    if (h->cfg.smoother == GMG_SMOOTHER_JACOBI) return (T)h->cfg.jacobi_omega;
+    return (T)cheby_step_coeffs(l.cheby_lambda, cheby_ratio(h), 0).c2;
+}
+
+// That step as a launch of its own (gmg_config::zero_guess_step): tmp = c * (b / diag) over all n_pad rows, for Chebyshev the direction p (the
+// level's residual vector: launch_cheby_steps) too.  It writes where the generic first step writes, so the sweeps behind it ping-pong as ever.
+template <class T>
+void launch_zero_step(gmg_handle h, Level& l, int d) {
+    const int ld = l.n_pad;
+    const T c = zero_step_coeff<T>(h, l);
+    ++h->zero_steps;
+    for_col_chunks(d, [&](int c0, int dc) {
+        DISPATCH_D(dc, DISPATCH_FLAG(WRITE_P, h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV, hipLaunchKernelGGL((gmgk::pointwise_zero_step<T, D, WRITE_P>),
+                                          dim3((ld + gmgk::kBlock - 1) / gmgk::kBlock), dim3(gmgk::kBlock), 0, h->stream, Prec<T>::diag(l), Prec<T>::b(l) + (size_t)c0 * ld,
+                                          Prec<T>::tmp(l) + (size_t)c0 * ld, Prec<T>::r(l) + (size_t)c0 * ld, ld, ld, c)));
+    });
+}
+
+// ask.from_zero (both pointwise smoothers): the iterate is the zero vector and x holds anything -- the first step is the zero step, enqueued here
+// unless the restriction into the level computed it (ask.first_done); either way its result is in tmp and the second step reads it there
+template <class T>
+void launch_jacobi_sweeps(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask = {}) {
     const int ld = l.n_pad;
     T* in = Prec<T>::x(l); T* out = Prec<T>::tmp(l);
     const T* b = Prec<T>::b(l);
-    for (int it = 0; it < iters; ++it) {
+    int it0 = 0;
+    if (ask.from_zero) {
+        if (!ask.first_done) launch_zero_step<T>(h, l, d);
+        std::swap(in, out);
+        it0 = 1;
+    }
+    for (int it = it0; it < iters; ++it) {
         for_col_chunks(d, [&](int c0, int dc) {
             DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::jacobi_sweep<T, D>), dim3(grid_for(l.Aoff.n_slices)), dim3(gmgk::kBlock), 0, h->stream,
                                               l.Aoff.slice_ptr, l.Aoff.col, Prec<T>::val(l.Aoff), Prec<T>::diag(l), b + (size_t)c0 * ld,
@@ -236,14 +266,20 @@ void launch_jacobi_sweeps(gmg_handle h, Level& l, int d, int iters) {
 // which is dead while the level is smoothed (the way down forms b - A x after the pre-smoothing, the restriction has consumed it before the
 // post-smoothing, and the accelerated loop writes it anew after the cycle).
 template <class T>
-void launch_cheby_steps(gmg_handle h, Level& l, int d, int iters) {
+void launch_cheby_steps(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask = {}) {
     const int ld = l.n_pad;
     T* in = Prec<T>::x(l); T* out = Prec<T>::tmp(l);
     const T* b = Prec<T>::b(l);
     T* p = Prec<T>::r(l);
     const int c16 = &l == &h->lv[0] ? l.Aoff.c16_sel() : 0;
     const double ratio = cheby_ratio(h);
-    for (int it = 0; it < iters; ++it) {
+    int it0 = 0;
+    if (ask.from_zero) {                               // (see launch_jacobi_sweeps; the zero step wrote p as well)
+        if (!ask.first_done) launch_zero_step<T>(h, l, d);
+        std::swap(in, out);
+        it0 = 1;
+    }
+    for (int it = it0; it < iters; ++it) {
         const ChebyStep st = cheby_step_coeffs(l.cheby_lambda, ratio, it);
         for_col_chunks(d, [&](int c0, int dc) {
             DISPATCH_D(dc, DISPATCH_C16(c16, DISPATCH_FLAG(FIRST, it == 0, hipLaunchKernelGGL((gmgk::cheby_step<T, D, FIRST, C16>), dim3(grid_for(l.Aoff.n_slices)),
@@ -357,16 +393,18 @@ bool launch_residual_delta(gmg_handle h, Level& l, int d, T* r, const SmoothDone
     return true;
 }
 
-// true when smoothing level l from a zero iterate needs no materialised zero vector (block sweeps, at least one of them)
+// true when smoothing level l from a zero iterate needs no materialised zero vector: block sweeps, or a pointwise smoother with
+// gmg_config::zero_guess_step (launch_zero_step) -- at least one sweep / step either way
 inline bool smooth_from_zero_ok(gmg_handle h, const Level& l, int iters) {
-    return iters > 0 && !pointwise_smoother(h->cfg) && l.ord.blocked;
+    if (pointwise_smoother(h->cfg)) return iters > 0 && h->cfg.zero_guess_step != 0;
+    return iters > 0 && l.ord.blocked;
 }
 
 template <class T = double>
 SmoothDone<T> launch_smooth(gmg_handle h, Level& l, int d, int iters, const SmoothAsk<T>& ask = {}) {
     if (iters <= 0) return {};
-    if (h->cfg.smoother == GMG_SMOOTHER_JACOBI) launch_jacobi_sweeps<T>(h, l, d, iters);
-    else if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV) launch_cheby_steps<T>(h, l, d, iters);
+    if (h->cfg.smoother == GMG_SMOOTHER_JACOBI) launch_jacobi_sweeps<T>(h, l, d, iters, ask);
+    else if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV) launch_cheby_steps<T>(h, l, d, iters, ask);
     else if (l.ord.blocked) return launch_block_sweeps<T>(h, l, d, iters, ask);
     else return launch_gs_sweeps<T>(h, l, d, iters, ask);
     return {};
@@ -428,6 +466,30 @@ template <class T>
 void launch_restrict(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, T* dst, bool src_il = false) {
     if (fine.R.lpr == 4) launch_restrict_lpr<T, 4>(h, fine, coarse, d, src, dst, src_il);
     else launch_restrict_lpr<T, 1>(h, fine, coarse, d, src, dst, src_il);
+}
+
+// Pointwise smoothers (gmg_config::zero_guess_step): may the restriction into `coarse` compute that level's zero step for the rows it writes
+// (transfer<.., STEP0>)?  The one rule: the level is smoothed from zero (smooth_from_zero_ok: a pointwise smoother with the field set and
+// pre_iters >= 1; the caller keeps the coarsest level out) and all columns are one chunk (d <= 4) -- with more, the separate zero step runs
+// (launch_zero_step), as it does on the coarsest-but-one level of a caller that restricts by hand.  Every layout of the restriction qualifies:
+// one or four lanes per row, with or without an output-row map, 16-bit codes or not, interleaved or column-major source.
+inline bool restrict_step0_ok(gmg_handle h, const Level& coarse, int d) {
+    return pointwise_smoother(h->cfg) && smooth_from_zero_ok(h, coarse, h->cfg.pre_iters) && d <= 4;
+}
+// coarse.b = U^T fine.r, and coarse.tmp (Chebyshev: and p) = the zero step on it, in one launch
+template <class T, int LPR>
+void launch_restrict_step0_lpr(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, bool src_il) {
+    const bool il = src_il && d > 1 && d <= 4;
+    const T c = zero_step_coeff<T>(h, coarse);
+    DISPATCH_D(d, DISPATCH_C16(fine.R.c16_sel(), DISPATCH_FLAG(XI, il, DISPATCH_FLAG(CHEB, h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV,
+                  hipLaunchKernelGGL((gmgk::transfer<T, D, 0, LPR, C16, (XI && D > 1), (CHEB ? 2 : 1)>), dim3(grid_for(fine.R.n_slices)), dim3(gmgk::kBlock), 0, h->stream,
+                                     fine.R.slice_ptr, fine.R.col, Prec<T>::val(fine.R), fine.R.row_of, src, fine.n_pad, Prec<T>::b(coarse), coarse.n_pad, 0, fine.R.n_slices, 1,
+                                     fine.R.col16, fine.R.win_base, fine.R.c16_arg(), Prec<T>::diag(coarse), Prec<T>::tmp(coarse), Prec<T>::r(coarse), c)))));
+}
+template <class T>
+void launch_restrict_step0(gmg_handle h, Level& fine, Level& coarse, int d, const T* src, bool src_il) {
+    if (fine.R.lpr == 4) launch_restrict_step0_lpr<T, 4>(h, fine, coarse, d, src, src_il);
+    else launch_restrict_step0_lpr<T, 1>(h, fine, coarse, d, src, src_il);
 }
 
 // coarse.b = U^T fine.r AND the first pre-sweep of the coarse level from the zero iterate, in one launch (kernels.hip.hpp::restrict_sweep0), where the
@@ -805,6 +867,12 @@ template <class T>
 bool restrict_into(gmg_handle h, int k, int d, bool il) {
     Level& l = h->lv[k];
     Level& c = h->lv[k + 1];
+    // (a pointwise smoother: the restriction's launch computes the level's zero step -- restrict_step0_ok; SmoothAsk::first_done means that result there)
+    if (k + 1 < h->L && restrict_step0_ok(h, c, d)) {
+        ++h->fused_step_restrictions;
+        launch_restrict_step0<T>(h, l, c, d, Prec<T>::r(l), il);
+        return true;
+    }
     const int fused = (k + 1 < h->L && smooth_from_zero_ok(h, c, h->cfg.pre_iters)) ? restrict_sweep0_kind<T>(h, l, c, d, il) : 0;
     if (fused) { ++h->fused_restrictions; launch_restrict_sweep0<T>(h, l, c, d, Prec<T>::r(l), il, fused); }
     else launch_restrict<T>(h, l, c, d, Prec<T>::r(l), Prec<T>::b(c), il);
@@ -812,15 +880,16 @@ bool restrict_into(gmg_handle h, int k, int d, bool il) {
 }
 
 // the way down from level k0.  first_done: the caller's restriction into level k0 ran that level's first pre-sweep (restrict_into's return
-// value: a caller that starts below level 0 restricted into level k0 itself); head_done: level 0's first colour launch is in the stream
+// value: a caller that starts below level 0 restricted into level k0 itself); head_done: level 0's first colour launch is in the stream;
+// x0_zero: level 0 starts from the zero vector too and its x holds anything (level0_zero_guess: the engine's own zero guesses)
 template <class T = double>
-void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, int head_done = 0) {
+void enqueue_down(gmg_handle h, int d, int k0 = 0, bool first_done = false, int head_done = 0, bool x0_zero = false) {
     const int L = h->L;
     for (int k = k0; k < L; ++k) {
         Level& l = h->lv[k];
         prof_mark(h);
         SmoothAsk<T> ask;
-        ask.from_zero = k > 0 && smooth_from_zero_ok(h, l, h->cfg.pre_iters);      // eps.setZero (:1072-1073) folded into the first sweep
+        ask.from_zero = (k > 0 || x0_zero) && smooth_from_zero_ok(h, l, h->cfg.pre_iters);      // eps.setZero (:1072-1073) folded into the first sweep
         if (k > 0 && !ask.from_zero) (void)hipMemsetAsync(Prec<T>::x(l), 0, sizeof(T) * (size_t)l.n_pad * d, h->stream);
         ask.first_done = first_done; ask.head_done = k == 0 ? head_done : 0;
         // d = 2 .. 4: the level-0 residual is written as an INTERLEAVED multi-vector (n x d row-major) -- only the restriction reads it, and a
@@ -1083,6 +1152,8 @@ int run_graph(gmg_handle h, int key, F&& enqueue) {
         enqueue();
         HIPCHK(hipStreamEndCapture(h->stream, &g));
         h->timing["graph_capture_ms"] += ms_since(tc);
+        // what this leg enqueues, counted: kernels, memsets and copies of the graph captured last (scripts/pointwise_ab.py reads a cycle's launch count here)
+        { size_t nodes = 0; if (hipGraphGetNodes(g, nullptr, &nodes) == hipSuccess) h->timing["graph_nodes"] = (double)nodes; else (void)hipGetLastError(); }
         tc = clk::now();
         HIPCHK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
         h->timing["graph_instantiate_ms"] += ms_since(tc);
@@ -1097,8 +1168,11 @@ int run_graph(gmg_handle h, int key, F&& enqueue) {
 // (result in h_norm after the stream is synchronised by the caller).
 // What the loop around the cycle knows -- head_done: this cycle's first colour launch is already in the stream (enqueue_head: never under a
 // graph); decide: the check's reduction also takes the loop's decision (CycleWatch; not the mixed-precision check: no head is eligible there).
+// zero_guess: the caller's x of level 0 is the zero vector by construction and holds anything (the preconditioner application of the CG loop); the
+// fp32 inner cycle always starts so.  Where the smoother can start without a materialised zero (level0_zero_guess) nothing zeroes or reads it.
+inline bool level0_zero_guess(gmg_handle h) { return pointwise_smoother(h->cfg) && h->L >= 1 && smooth_from_zero_ok(h, h->lv[0], h->cfg.pre_iters); }
 template <class T>
-int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done, const CycleWatch* decide) {
+int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done, const CycleWatch* decide, bool zero_guess = false) {
     int rc;
     const int nt = norm_type < 0 ? 9 : norm_type;
     constexpr bool mixed = sizeof(T) == 4;
@@ -1107,7 +1181,8 @@ int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done,
     const int fold_type = foldable ? norm_type : -1;
     // mixed precision: the fp32 cycle starts from a zero guess on the defect b32 = b - A x (already in place), its
     // result is added to the fp64 iterate, and the new defect + its norms are formed in one fp64 pass
-    auto head = [&] { if (mixed) (void)hipMemsetAsync(h->lv[0].x32, 0, sizeof(float) * (size_t)h->lv[0].n_pad * d, h->stream); };
+    const bool x0_zero = (mixed || zero_guess) && level0_zero_guess(h);
+    auto head = [&] { if (mixed && !x0_zero) (void)hipMemsetAsync(h->lv[0].x32, 0, sizeof(float) * (size_t)h->lv[0].n_pad * d, h->stream); };
     // (folded: what the way up returned -- both in one enqueue body, which under a graph runs at capture only)
     auto tail = [&](int& err, int folded) {
         if (mixed) {
@@ -1121,13 +1196,13 @@ int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done,
         int err = GMG_OK;
         rc = run_graph(h, key_salt + G_FULL * 10000 + d * 10 + nt, [&] {
             head();
-            enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done);
+            enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done, x0_zero);
             enqueue_coarse_device<T>(h, d);
             tail(err, enqueue_up<T>(h, d, 0, fold_type));
         });
         return rc ? rc : err;
     }
-    if ((rc = run_graph(h, key_salt + G_DOWN * 10000 + d * 10, [&] { head(); enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done); }))) return rc;
+    if ((rc = run_graph(h, key_salt + G_DOWN * 10000 + d * 10, [&] { head(); enqueue_down<T>(h, d, /*k0*/ 0, /*first_done*/ false, head_done, x0_zero); }))) return rc;
     if ((rc = coarse_host_begin<T>(h, d))) return rc;              // (polled: the way up is enqueued behind a gate the host opens in _serve)
     int err = GMG_OK;
     rc = run_graph(h, key_salt + G_UP * 10000 + d * 10 + nt, [&] { tail(err, enqueue_up<T>(h, d, 0, fold_type)); });
@@ -1233,7 +1308,8 @@ void pcg_exchange(gmg_handle h) {
 
 // One CG step behind the cycle, owners exchanged: lv[0].b holds r, lv[0].x holds z = cycle(r, 0), pcg.x the iterate, pcg.b the true b.
 // first: the first iteration of the solve; fresh: r was recomputed from the iterate.  Leaves the new iterate in pcg.x, the recurrence residual
-// in lv[0].b, zeros in lv[0].x and the check's sums on their way to h_norm (wait_norm).
+// in lv[0].b, zeros in lv[0].x (z itself where the next cycle starts from zero without them: level0_zero_guess) and the check's sums on their way
+// to h_norm (wait_norm).
 int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
     auto& a = h->pcg;
     Level& l = h->lv[0];
@@ -1249,7 +1325,9 @@ int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
         DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, r + off, z + off, ld, n_pairs, a.partials));
         hipLaunchKernelGGL(gmgk::pcg_reduce_beta, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, rho + c0, beta + c0, restart + c0,
                            (int)first, (int)fresh, restarts);
-        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_direction<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, z + off, a.p + off, beta + c0, ld, n_pairs));
+        // (the next cycle's zero guess: written here unless that cycle starts from zero by itself)
+        DISPATCH_D(dc, DISPATCH_FLAG(ZERO_Z, !level0_zero_guess(h), hipLaunchKernelGGL((gmgk::pcg_direction<D, ZERO_Z>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream,
+                                          z + off, a.p + off, beta + c0, ld, n_pairs)));
     });
     launch_spmv<double>(h, l, d, 0, nullptr, a.p.get(), q);
     for_col_chunks(d, [&](int c0, int dc) {

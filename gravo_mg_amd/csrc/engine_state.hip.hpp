@@ -301,7 +301,9 @@ struct gmg_solver_s {
     DevBuf<int> d_tri_perm;
     int tri_n = -1;                                        // n_L the four buffers are sized for (-1: none)
     bool coarse_triangle = false;                          // coarse_device, applied from d_tri (decided per system)
-    int64_t fused_restrictions = 0;                       // restrictions enqueued together with the next level's first pre-sweep (restrict_into; timing key "restrict_sweeps_fused")
+    int64_t zero_steps = 0;                               // separate zero-step launches of a pointwise smoother enqueued (gmg_config::zero_guess_step; timing key "zero_guess_steps")
+    int64_t fused_step_restrictions = 0;                  // restrictions enqueued that computed the coarse level's zero step too (restrict_into; timing key "restrict_steps_fused")
+    int64_t fused_restrictions = 0;                      // restrictions enqueued together with the next level's first pre-sweep (restrict_into; timing key "restrict_sweeps_fused")
     bool coarse_device = false;                            // the coarsest solve of the live system runs on the device (gmg_config::coarse_mode, decided per system)
     std::vector<double> coarse_work;
     std::unique_ptr<SpinTeam> coarse_helper;        // the other threads of the coarsest back-substitution, armed for the duration of a solve (HelperScope)
@@ -497,6 +499,10 @@ void drop_device_transfers(gmg_handle h) {
     h->dU_flagged = false;
 }
 
+// Handles whose level 0 takes the locality renumbering of gmg_config::reorder_fine: the multicolour smoother, and a pointwise smoother that asked
+// for it (gmg_config::reorder_pointwise) -- the latter's level 0 is one class of rows in the base order, nothing is coloured.
+inline bool locality_reorder_smoother(const gmg_config& c) { return c.smoother == GMG_SMOOTHER_MULTICOLOR_GS || c.reorder_pointwise != 0; }
+
 // Patches of every blocked level k >= 1 (see coarse_point_graph): depend on the hierarchy and on block_rows only.
 void build_patches(gmg_handle h) {
     const int L = h->L;
@@ -529,7 +535,7 @@ void build_patches(gmg_handle h) {
                 if (n_patches > 0 && (long)G.n_outer * 4 < n_patches * (long)h->cfg.block_rows) h->patches[k] = PatchSet();
                 tr(("grow patches l" + std::to_string(k)).c_str(), t0);
             }));
-    if (mc && h->cfg.reorder_fine != 0 && L > 0)
+    if (locality_reorder_smoother(h->cfg) && h->cfg.reorder_fine != 0 && L > 0)
         jobs.push_back(std::async(std::launch::async, [h, L, &Urows, &tr] {
             auto t0 = clk::now();
             Compressed GL = coarse_point_graph(h->U[L - 1], Urows[L - 1]);

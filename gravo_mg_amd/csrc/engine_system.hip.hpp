@@ -300,6 +300,7 @@ int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, boo
     const int L = h->L;
     int rc;
     h->timing["coarsest_solve"] = ms_factor;
+    h->timing["fine_level_reordered"] = h->lv[0].ord.reordered ? 1.0 : 0.0;      // level 0 follows a locality order (reorder_fine; gmg_config::reorder_pointwise)
     h->coarse_device = want_coarse_device(h, h->lv[L].A.n_outer);
     h->timing["coarse_on_device"] = h->coarse_device ? 1.0 : 0.0;
     h->coarse_triangle = h->coarse_device && want_coarse_triangle(h);
@@ -667,13 +668,16 @@ private:
     // on the device before the ordering task starts.
     int renumber_level0() {
         t0 = clk::now();
-        reorder0 = mc && !ord_hit && !blocked0 && wants_locality_reorder(PatternView{n, colptr, rowidx}, h->cfg.reorder_fine);
+        // (gmg_config::reorder_pointwise: a pointwise smoother takes the same decision and the same base order; its level 0 is not coloured)
+        reorder0 = locality_reorder_smoother(h->cfg) && !ord_hit && !blocked0 && wants_locality_reorder(PatternView{n, colptr, rowidx}, h->cfg.reorder_fine);
         if (reorder0) e.ahead.cancel();                // (the level is coloured along another visit order: the loop started on the caller's order is of no use)
         if (e.early_A0.ptr && device_setup && h->cfg.device_rap) { h->lv[0].dA = std::move(e.early_A0); e.early_A0 = {}; A0_uploaded = true; }
         { const int rc = color_level0_on_device(); if (rc != GMG_OK) return rc; }
         // (h->cluster_order is only read once the patches are ready: build_patches may still be writing it)
         const bool have_bfs = (int)h->bfs_order.size() == n, have_cluster = h->patches_ready && (int)h->cluster_order.size() == n;
         h->base_order_choice = (reorder0 && h->patches_ready && have_bfs && !have_cluster) ? 1 : 0;
+        // (a renumbered pointwise handle writes the three keys of the choice on every route, scored or not)
+        if (reorder0 && !mc) { h->timing["base_order_score_cluster"] = h->timing["base_order_score_bfs"] = 0.0; h->timing["base_order_choice"] = h->base_order_choice; }
         if (reorder0 && have_bfs && have_cluster && !(device_setup && h->cfg.device_rap)) {
             // host-planner path: the same decision from the host twin of the device score (choose_base_order)
             unsigned long long sc[2], sb[2];
@@ -688,9 +692,10 @@ private:
             int rc = A0_uploaded ? GMG_OK : upload_csr_raw(h, h->lv[0].dA, n, colptr, rowidx, val);
             if (rc == GMG_OK) { A0_uploaded = true; rc = choose_base_order(h, h->lv[0].dA, n); }
             // (colours from the device depend on no visit order: the pattern need not come back permuted for a host loop to walk it)
-            if (rc == GMG_OK && !colored_dev) rc = device_permute_pattern(h, h->lv[0].dA, n, colptr[n]);
+            // (... nor for a pointwise smoother, which colours nothing: make_ordering puts its one class in base order)
+            if (rc == GMG_OK && !colored_dev && mc) rc = device_permute_pattern(h, h->lv[0].dA, n, colptr[n]);
             if (rc != GMG_OK) return rc;
-            permuted0 = !colored_dev;
+            permuted0 = !colored_dev && mc;
             if (permuted0) mark("permuted_pattern");
         }
         return GMG_OK;

@@ -1214,6 +1214,29 @@ __global__ __launch_bounds__(kBlock) void cheby_step(const int64_t* __restrict__
     }
 }
 
+// The first step of a pointwise smoother on a ZERO iterate (gmg_config::zero_guess_step): what jacobi_sweep / cheby_step<.., FIRST = true> evaluate
+// with acc = 0 and x_i = 0, the same operations in the same order -- the off-diagonal sum and dg * x_i are (+)0, b_i - 0 is b_i, and 0 + v is v
+// up to the sign of a zero --:  Jacobi  x_i = omega * (b_i / dg),  Chebyshev  p_i = c2 * (b_i / dg), x_i = p_i  (c: omega or c2).  One copy, so the
+// streaming kernel and the restriction that computes the step for its own rows (transfer_slice<.., STEP0>) agree bit for bit.
+template <class T> __device__ __forceinline__ T zero_step_row(T bi, T dg, T c) { return c * (bi / dg); }
+
+// ... as a streaming kernel over all n_pad rows of a level, one row per thread: no slice pointers, no operator.  Padding rows have b = 0 and
+// diag = 1 and stay zero.  WRITE_P: Chebyshev (the value is the direction p as well); Jacobi has no p.
+template <class T, int D, bool WRITE_P>
+__global__ __launch_bounds__(kBlock) void pointwise_zero_step(const T* __restrict__ diag, const T* __restrict__ b, T* __restrict__ x_out, T* __restrict__ p,
+                                                              int ld, int n_pad, T c) {
+    const int row = blockIdx.x * kBlock + threadIdx.x;
+    if (row >= n_pad) return;
+    const T dg = diag[row];
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+        const int64_t i = row + (int64_t)k * ld;
+        const T v = zero_step_row(b[i], dg, c);
+        if constexpr (WRITE_P) p[i] = v;
+        x_out[i] = v;
+    }
+}
+
 // MODE 0: y = A x      MODE 1: y = b - A x   (gravomg/src/multigrid_solver.cpp:1066)
 // LPR = lanes per row of the SELL layout (1, or 4 on the coarse levels): slices then hold 64 / LPR rows.
 template <class T, int D, int MODE, int LPR, int C16 = 0, int YI = 0>
@@ -1257,10 +1280,15 @@ __global__ __launch_bounds__(kBlock) void spmv_full_list(const int64_t* __restri
 //                       ADD = 1: y[out_row] += sum val * x[col]  (prolongation x += U e, :1082)
 // row_of (may be null) maps the slice row to the output row (-1 = none); ldx/ldy are the leading
 // dimensions of the source / destination level.  LPR as in spmv_full.
-template <class T, int D, int ADD, int LPR, int C16 = 0, int XI = 0>
+// STEP0 (restriction only, ADD = 0; gmg_config::zero_guess_step): the lane that writes y[row] = acc -- the coarse level's right-hand side -- also writes that
+// level's first smoothing step from the zero iterate for the row, zero_step_row(acc, diag[row], c), to x0 (1: Jacobi; 2: Chebyshev, and to p0).  The
+// value stored to y is the value the step would load.  Slice rows without an output row write nothing; the padding rows of x0 / p0 are zero and stay so.
+template <class T, int D, int ADD, int LPR, int C16 = 0, int XI = 0, int STEP0 = 0>
 __device__ __forceinline__ void transfer_slice(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col, const T* __restrict__ val,
                                                const int* __restrict__ row_of, const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy, int s,
-                                               const unsigned* __restrict__ col16 = nullptr, const int* __restrict__ win_base = nullptr, int c16_arg = 0) {
+                                               const unsigned* __restrict__ col16 = nullptr, const int* __restrict__ win_base = nullptr, int c16_arg = 0,
+                                               const T* __restrict__ diag0 = nullptr, T* __restrict__ x0 = nullptr, T* __restrict__ p0 = nullptr, T c0 = (T)0) {
+    static_assert(!(ADD && STEP0), "the zero step rides on the restriction only");
     const int lane = threadIdx.x & 63;
     const int srow = s * (64 / LPR) + lane / LPR;
     T acc[D];
@@ -1271,21 +1299,29 @@ __device__ __forceinline__ void transfer_slice(const int64_t* __restrict__ slice
     // instantiation never takes an output-row map (slice row == output row: unique by construction)
     const int row = (!ADD && row_of) ? row_of[srow] : srow;
     if (row < 0) return;
+    T dg0 = (T)1;
+    if constexpr (STEP0 != 0) dg0 = diag0[row];
 #pragma unroll
     for (int c = 0; c < D; ++c) {
         if (ADD) y[row + (int64_t)c * ldy] += acc[c];
         else y[row + (int64_t)c * ldy] = acc[c];
+        if constexpr (STEP0 != 0) {
+            const T v = zero_step_row(acc[c], dg0, c0);
+            if constexpr (STEP0 == 2) p0[row + (int64_t)c * ldy] = v;
+            x0[row + (int64_t)c * ldy] = v;
+        }
     }
 }
-template <class T, int D, int ADD, int LPR, int C16 = 0, int XI = 0>
+template <class T, int D, int ADD, int LPR, int C16 = 0, int XI = 0, int STEP0 = 0>
 __global__ __launch_bounds__(kBlock) void transfer(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,
                                                    const T* __restrict__ val, const int* __restrict__ row_of,
                                                    const T* __restrict__ x, int ldx, T* __restrict__ y, int ldy,
                                                    int slice_begin, int slice_end, int xcd_swizzle, const unsigned* __restrict__ col16 = nullptr,
-                                                   const int* __restrict__ win_base = nullptr, int c16_arg = 0) {
+                                                   const int* __restrict__ win_base = nullptr, int c16_arg = 0,
+                                                   const T* __restrict__ diag0 = nullptr, T* __restrict__ x0 = nullptr, T* __restrict__ p0 = nullptr, T c0 = (T)0) {
     const int s = slice_begin + wave_slice(slice_end - slice_begin, xcd_swizzle);
     if (s >= slice_end) return;
-    transfer_slice<T, D, ADD, LPR, C16, XI>(slice_ptr, col, val, row_of, x, ldx, y, ldy, s, col16, win_base, c16_arg);
+    transfer_slice<T, D, ADD, LPR, C16, XI, STEP0>(slice_ptr, col, val, row_of, x, ldx, y, ldy, s, col16, win_base, c16_arg, diag0, x0, p0, c0);
 }
 template <class T, int D, int ADD, int LPR>
 __global__ __launch_bounds__(kBlock) void transfer_list(const int64_t* __restrict__ slice_ptr, const int* __restrict__ col,

@@ -3,7 +3,7 @@
 // every vector and left zero), for one group of <= 4 columns, z = cycle(rhs = r, x = 0) being there already:
 //
 //   pcg_rz          partial sums of rho = <r, z>                              -> pcg_reduce_beta:  beta = rho / rho_prev (0: a fresh recurrence)
-//   pcg_direction   p = z + beta p (beta = 0: p = z, the old p is not read);  z = 0 (the next cycle's zero guess)
+//   pcg_direction   p = z + beta p (beta = 0: p = z, the old p is not read);  z = 0 (the next cycle's zero guess; not with gmg_config::zero_guess_step)
 //   (q = A p: the level-0 product, engine_cycle.hip.hpp::launch_spmv)
 //   pcg_pq          partial sums of <p, q>                                    -> pcg_reduce_alpha: alpha = rho / <p, q> or the guard (alpha = 0)
 //   pcg_update      x += alpha p,  r -= alpha q (alpha = 0: neither p nor q is read),  partial sums of w r^2, w b^2 (the residual check's)
@@ -37,8 +37,9 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_dot(const double* __restrict_
     accel_block_store<DC>(acc, DC, partials);
 }
 
-// p = z + beta p (a column with beta = 0 writes p = z without reading p: what is there may be anything); z = 0 afterwards
-template <int DC>
+// p = z + beta p (a column with beta = 0 writes p = z without reading p: what is there may be anything); ZERO_Z: z = 0 afterwards -- without it
+// z is only read (three vector passes instead of four): the next cycle starts from zero by itself (gmg_config::zero_guess_step)
+template <int DC, bool ZERO_Z = true>
 __global__ __launch_bounds__(kAccelBlock) void pcg_direction(double* __restrict__ z, double* __restrict__ p, const double* __restrict__ beta, int ld,
                                                              int n_pairs) {
     double bt[DC];
@@ -54,7 +55,7 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_direction(double* __restrict_
                 pn.x += bt[c] * po.x; pn.y += bt[c] * po.y;
             }
             accel_st2(p, at, pn);
-            accel_st2(z, at, make_double2(0.0, 0.0));
+            if constexpr (ZERO_Z) accel_st2(z, at, make_double2(0.0, 0.0));
         }
     }
 }

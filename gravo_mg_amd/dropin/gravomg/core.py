@@ -307,7 +307,11 @@ class MultigridSolver(object):
         accelerate (0 = default: the reference's solve loop; m in 1..4: truncated GCR around the V-cycle -- each cycle's step is orthogonalised against the last m - 1 and scaled so
         that the tested residue is minimal and cannot grow; fp64 and one device only, gmg_config::accelerate),
         pcg (0 = default; 1: conjugate gradients preconditioned by the V-cycle -- needs smoother 1 or 2 and equal pre / post iteration counts, which make the cycle a symmetric
-        positive definite operator; converges for every symmetric positive definite system; not together with accelerate, fp64 and one device only, gmg_config::pcg)."""
+        positive definite operator; converges for every symmetric positive definite system; not together with accelerate, fp64 and one device only, gmg_config::pcg),
+        reorder_pointwise (0 = default; 1: with smoother 1 or 2 the finest level is renumbered for locality as it is for the multicolour smoother -- inputs in
+        arbitrary vertex order, point clouds; gmg_config::reorder_pointwise),
+        zero_guess_step (0 = default; 1: with smoother 1 or 2 a first step on a zero guess is c * b / diag, no zero vector is written or read; the same
+        iterates, gmg_config::zero_guess_step)."""
         self.solver.set_engine_option(str(key), float(value))
         if str(key) == "device":
             self._device = int(value)

@@ -73,7 +73,8 @@ typedef struct {
     int post_iters;        /* MultigridSolver::postIters (core.cpp:56) */
     int coarse_mode;       /* GMG_COARSE_*: where the coarsest direct solve is applied (default GMG_COARSE_AUTO; GMG_COARSE_DEVICE_TRIANGLE = 3: on the device from
                               the packed lower triangle of the inverse -- half the memory and bytes, one more launch); other values: the host */
-    int use_graph;         /* 1: replay the V-cycle legs from captured hipGraphs; 0 (default): plain stream launches */
+    int use_graph;         /* 1: replay the V-cycle legs from captured hipGraphs (timing key "graph_nodes": kernels + memsets + copies of the leg captured
+                              last); 0 (default): plain stream launches */
     int sigma;             /* length-sorting window (rows) inside the colour classes of a colour-major level (multiple of 64; 0 = no sorting,
                               the default: sorting rows by length trades SELL padding for locality of the gathers, and on the irregular
                               workloads measured the locality is worth more -- 2 M point cloud: fine sweep 131 -> 108 us, residual 109 -> 82 us) */
@@ -161,7 +162,28 @@ typedef struct {
                               last; otherwise, and with 0, the head is the first colour launch.  Timing key "heads_folded" counts the folded heads
                               ("heads_enqueued" counts every launch enqueued ahead of the decision, folded or not).  Added after accelerate, in front of which
                               it stands: accelerate stays the last field, and a binding built against another edition is refused by gmg_config_size */
-    int pcg;               /* 0 (default): the solve loop as in the reference.  1: gmg_solve, gmg_solve_x0_rhs and gmg_solve_device run preconditioned
+    int reorder_pointwise; /* 0 (default): the locality renumbering of level 0 (reorder_fine) is made for the multicolour smoother only; a pointwise smoother
+                              (GMG_SMOOTHER_CHEBYSHEV, GMG_SMOOTHER_JACOBI) keeps the caller's numbering.  1: such a handle takes the same decision
+                              (reorder_fine 0 / 1 / 2 as documented there) and the same choice between the hierarchy's cluster order and the breadth-first
+                              order (timing keys "base_order_choice", "base_order_score_cluster", "base_order_score_bfs"); level 0 is then one class of
+                              rows in that order -- nothing is coloured -- and every layout, transfer and permutation follows it.  The smoother's
+                              iterates do not depend on the numbering beyond the rounding of a changed summation order; its gathers do.
+                              Without effect with the multicolour smoother.  Every gmg_set_system writes the timing key "fine_level_reordered" (0 / 1:
+                              level 0 follows a locality order), on every handle.  Values other than 0 / 1: GMG_ERR_INVALID (gmg_last_error(NULL) names
+                              the field).  In front of pcg, like fold_head */
+    int zero_guess_step;   /* 0 (default): a pointwise smoother that starts from the zero vector reads a materialised one (a memset per coarse level and
+                              cycle, and a first step that multiplies the operator by zeros).  1, with a pointwise smoother and pre_iters >= 1: that
+                              first step is x = c (b / diag) (c = omega for Jacobi, the first Chebyshev coefficient, which also gives p) -- the
+                              arithmetic of the generic step on a zero iterate, so the bits are those of 0 up to the sign of a zero.  It runs as a
+                              streaming kernel without the operator, or inside the restriction's launch where that is one launch for all columns
+                              (engine_cycle.hip.hpp::restrict_step0_ok); the memsets go.  On level 0 where the engine supplies the zero guess: the
+                              preconditioner application of pcg = 1 (whose direction update then no longer writes zeros) and the fp32 inner cycle of
+                              inner_precision = 1.  gmg_smooth_residual with from_zero != 0 takes it too.  gmg_vcycle, gmg_run_cycles, gmg_solve
+                              without pcg and accelerate start level 0 from the caller's iterate as before.  Without effect with the multicolour
+                              smoother.  Timing keys "zero_guess_steps" (separate zero-step launches) and "restrict_steps_fused" (restrictions that
+                              computed the step), cumulative per handle like "restrict_sweeps_fused", zero with 0.  Values other than 0 / 1:
+                              GMG_ERR_INVALID (gmg_last_error(NULL) names the field).  In front of pcg, like fold_head */
+    int pcg;              /* 0 (default): the solve loop as in the reference.  1: gmg_solve, gmg_solve_x0_rhs and gmg_solve_device run preconditioned
                               conjugate gradients with the handle's V-cycle as the preconditioner, per right-hand-side column:
                                 r = b - A x0;  repeat:  z = cycle(rhs = r, x = 0);  rho = <r, z>;  beta = rho / rho_prev (0 in a fresh recurrence);
                                 p = z + beta p;  q = A p;  alpha = rho / <p, q>;  x += alpha p;  r -= alpha q;  residue from sum w r^2 / sum w b^2
