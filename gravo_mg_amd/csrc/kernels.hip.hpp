@@ -222,6 +222,50 @@ template <class T> __device__ __forceinline__ T gs_row(T bi, T acc, T dg, T omeg
 // gs_color_residual, the fp32 right-hand side of residual_norm_slices<MODE 1>): the kernels that replace a pass of another agree with it bit for bit.
 template <class T> __device__ __forceinline__ T row_ax(T acc, T dg, T xi) { return acc + dg * xi; }
 __device__ __forceinline__ double norm_term(double v, double w) { return (v * w) * v; }      // a row's term of the check's sums, w v^2 (v = r_i or b_i)
+
+// ---- a row's own operands: diag[row], weight[row], b[row + c ld], x[row + c ld] (or the y a prolongation adds to) ------------------------------
+// Their addresses follow from the slice number and the lane alone, so a wave can request them BEFORE its row's dot product instead of after
+// it: written behind the dot they are a third dependent trip to memory (operator stream -> gathers -> these; streamed operands, a full HBM
+// miss) that the last waves of every launch and the small launches of the lower levels pay on their critical path -- the compiler leaves the
+// loads where the source has them, the dot sits in basic blocks of its own (width switch, group loop).  No byte more, no operation changed.
+// own_row_load<.., EARLY, 0> stands in front of row_dot_sel and own_row_load<.., EARLY, 1> behind it; each operand is loaded by exactly one
+// of the two.  EARLY = how many are requested in front: 0 none (the code as it was), 1 diag and weight, 2 also b, 3 also x.
+// OwnEarly gives the value per instantiation, by the rule that no instantiation may pay for it with a wave per SIMD or with scratch
+// (scripts/kernel_resources.py; the listings of all four values are summarised in profiles/README.md, own_row_loads/):
+//   * D = 1: everything, except gs_color_commit (60 registers already: AltRows) and gs_color_norm (58: the sums) on the index paths that
+//     decode through a 32-bit prefix or not at all (C16 0, 1, 3) -- 8 or 10 registers more are a wave less there; they take diag (+ b);
+//   * D >= 2: nothing.  These instantiations sit 2-10 registers under their occupancy step (84-90 of 96 at D = 2 / 3, 60-62 of 64 at
+//     D = 4, 60-64 of the 64 that the norm kernels' launch bound allows) and even diag alone tips some of them: they stay as they were.
+// Safe for the x of the sweep kernels (not __restrict__: the launch writes it): no other lane or workgroup of a launch writes this lane's
+// row -- rows of a colour do not couple, and gs_color_commit's appended workgroups write rows of the first colour only, which the working
+// blocks of that launch neither own nor read from x.  Padding rows are in bounds (n_pad rows per column).  want_*: wave-uniform.
+template <class T, int D> struct OwnRow { T dg, w; T b[D], x[D]; };
+enum { kOwnRow = 0, kOwnCommit = 1, kOwnColorNorm = 2 };
+template <int D, int FAMILY = kOwnRow, int C16 = 0> struct OwnEarly {
+    static constexpr bool flagged = C16 == 2 || C16 == 4;
+    static constexpr int value = D != 1 ? 0 : FAMILY == kOwnCommit ? (flagged ? 3 : C16 == 0 ? 2 : 1) : FAMILY == kOwnColorNorm ? (flagged ? 3 : 1) : 3;
+};
+template <class T, int D, int EARLY, int PHASE>
+__device__ __forceinline__ void own_row_load(OwnRow<T, D>& o, const T* __restrict__ diag, const T* b, const T* x, const T* __restrict__ weight,
+                                             int row, int ld, bool want_b, bool want_x, bool want_dg = true) {
+    if constexpr ((EARLY >= 1) == (PHASE == 0)) {
+        if (want_dg) o.dg = diag[row];
+        o.w = weight ? weight[row] : (T)1.0;
+    }
+    if constexpr ((EARLY >= 2) == (PHASE == 0)) {
+        if (want_b) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) o.b[c] = b[row + (int64_t)c * ld];
+        }
+    }
+    if constexpr ((EARLY >= 3) == (PHASE == 0)) {
+        if (want_x) {
+#pragma unroll
+            for (int c = 0; c < D; ++c) o.x[c] = x[row + (int64_t)c * ld];
+        }
+    }
+}
+
 // The 2 D sums of the NW waves of a block -> partials[slot][2 D]: shuffle tree inside the wave, then the wave sums in index order.  All threads of the
 // block call it (one barrier); `red` is the caller's LDS; SLOT is the type the caller has the slot in (unsigned blockIdx.x or int: widened here, as before).
 // (residual_norm_partials keeps a copy of these lines: with the call, two of its four instantiations were scheduled differently.)
@@ -263,28 +307,27 @@ __global__ __launch_bounds__(kBlock) void gs_color(const int64_t* __restrict__ s
     const int lane = threadIdx.x & 63;
     const int row = s * 64 + lane;
     T acc[D];
+    constexpr int EARLY = OwnEarly<D>::value;
+    const bool relax = OM != 0 || omega != (T)1.0;                  // kernel argument: wave-uniform.  The plain update reads no x_i
+    OwnRow<T, D> own;
+    own_row_load<T, D, EARLY, 0>(own, diag, b, x, nullptr, row, ld, true, relax);
     row_dot_sel<T, D, (FINE >= 2 ? FINE - 1 : 0)>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);      // FINE 2 / 3: level 0 with 16-bit column codes (row_dot_sel mode 1 / 2)
-    const T dg = diag[row];
+    own_row_load<T, D, EARLY, 1>(own, diag, b, x, nullptr, row, ld, true, relax);
+    const T dg = own.dg;
     if constexpr (OM != 0) {
         // hybrid Gauss-Seidel of a partitioned level 0 (engine_dist.hip.hpp::p2p_smooth): rows whose bit is set in plain_rows[slice] couple to rows of
         // another rank, whose values are a sweep old -- a Jacobi coupling, which over-relaxation amplifies: those rows take the plain update
         const T om = (plain_rows[s] >> lane) & 1ull ? (T)1.0 : omega;
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
-            const T xi = x[row + (int64_t)c * ld];
-            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, om, xi);
-        }
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(own.b[c], acc[c], dg, om, own.x[c]);
         return;
     }
-    if (omega == (T)1.0) {                 // kernel argument: a scalar branch.  The reference's update, no read of x_i
+    if (!relax) {                          // a scalar branch.  The reference's update
 #pragma unroll
-        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg);
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(own.b[c], acc[c], dg);
     } else {                               // successive over-relaxation: x_i <- x_i + omega (x_i^GS - x_i)
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
-            const T xi = x[row + (int64_t)c * ld];
-            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
-        }
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(own.b[c], acc[c], dg, omega, own.x[c]);
     }
 }
 
@@ -321,17 +364,19 @@ __global__ __launch_bounds__(kBlock) void gs_color_commit(const int64_t* __restr
     AltRows<double> alt;
     alt.shifted = xh - (int64_t)hb * 64; alt.lo = (unsigned)hb * 64u; alt.n = (unsigned)hrows;
     double acc[D];
+    constexpr int EARLY = OwnEarly<D, kOwnCommit, C16>::value;
+    const bool relax = omega != 1.0;
+    OwnRow<double, D> own;
+    own_row_load<double, D, EARLY, 0>(own, diag, b, x, nullptr, row, ld, true, relax);      // (a row of the second colour: the commit blocks do not write it)
     row_dot_sel<double, D, C16, DotGroup<D>::value, 0, true>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc, alt);
-    const double dg = diag[row];
-    if (omega == 1.0) {
+    own_row_load<double, D, EARLY, 1>(own, diag, b, x, nullptr, row, ld, true, relax);
+    const double dg = own.dg;
+    if (!relax) {
 #pragma unroll
-        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg);
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(own.b[c], acc[c], dg);
     } else {
 #pragma unroll
-        for (int c = 0; c < D; ++c) {
-            const double xi = x[row + (int64_t)c * ld];
-            x[row + (int64_t)c * ld] = gs_row(b[row + (int64_t)c * ld], acc[c], dg, omega, xi);
-        }
+        for (int c = 0; c < D; ++c) x[row + (int64_t)c * ld] = gs_row(own.b[c], acc[c], dg, omega, own.x[c]);
     }
 }
 
@@ -357,14 +402,18 @@ __global__ __launch_bounds__(kBlock) void gs_color_norm(const int64_t* __restric
     if (s < slice_end) {
         const int row = s * 64 + lane;
         double acc[D];
+        constexpr int EARLY = OwnEarly<D, kOwnColorNorm, C16>::value;
+        const bool relax = omega != 1.0;
+        OwnRow<double, D> own;
+        own_row_load<double, D, EARLY, 0>(own, diag, b, x, weight, row, ld, true, relax);
         row_dot_sel<double, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
-        const double dg = diag[row];
-        const double w = weight ? weight[row] : 1.0;
+        own_row_load<double, D, EARLY, 1>(own, diag, b, x, weight, row, ld, true, relax);
+        const double dg = own.dg;
+        const double w = own.w;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-            const double bi = b[row + (int64_t)c * ld];
-            const double xi = x[row + (int64_t)c * ld];
-            const double xn = omega == 1.0 ? gs_row(bi, acc[c], dg) : gs_row(bi, acc[c], dg, omega, xi);
+            const double bi = own.b[c];
+            const double xn = !relax ? gs_row(bi, acc[c], dg) : gs_row(bi, acc[c], dg, omega, own.x[c]);
             x[row + (int64_t)c * ld] = xn;
             const double r = row_ax(acc[c], dg, xn) - bi;            // residual_norm_slices' own functions, on the same operands
             sums[2 * c] = norm_term(r, w);
@@ -388,14 +437,19 @@ __global__ __launch_bounds__(kBlock) void gs_color_residual(const int64_t* __res
     const int lane = threadIdx.x & 63;
     const int row = s * 64 + lane;
     double acc[D];
+    constexpr int EARLY = OwnEarly<D>::value;
+    const bool relax = omega != 1.0;
+    OwnRow<double, D> own;
+    own_row_load<double, D, EARLY, 0>(own, diag, b, x, nullptr, row, ld, true, relax);
     row_dot_sel<double, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
-    const double dg = diag[row];
+    own_row_load<double, D, EARLY, 1>(own, diag, b, x, nullptr, row, ld, true, relax);
+    const double dg = own.dg;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        const double bi = b[row + (int64_t)c * ld];
+        const double bi = own.b[c];
         double xn;
-        if (omega == 1.0) xn = gs_row(bi, acc[c], dg);
-        else { const double xi = x[row + (int64_t)c * ld]; xn = gs_row(bi, acc[c], dg, omega, xi); }
+        if (!relax) xn = gs_row(bi, acc[c], dg);
+        else xn = gs_row(bi, acc[c], dg, omega, own.x[c]);
         x[row + (int64_t)c * ld] = xn;
         const double ax = row_ax(acc[c], dg, xn);
         r[YI ? (int64_t)row * D + c : row + (int64_t)c * ld] = bi - ax;           // (YI: the residual as an interleaved multi-vector, what the restriction gathers from)
@@ -1246,13 +1300,18 @@ __device__ __forceinline__ void spmv_full_slice(const int64_t* __restrict__ slic
     const int lane = threadIdx.x & 63;
     const int row = s * (64 / LPR) + lane / LPR;
     T acc[D];
+    constexpr int EARLY = OwnEarly<D>::value;
+    const bool mine = LPR == 1 || (lane & 3) == 0;                   // quad layout: the lane that stores the row is the one that needs its operands
+    OwnRow<T, D> own;
+    if (mine) own_row_load<T, D, EARLY, 0>(own, diag, b, x, nullptr, row, ld, MODE == 1, true);
     row_dot_sel<T, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
     if (LPR == 4) { quad_reduce<T, D>(acc); if (lane & 3) return; }
-    const T dg = diag[row];
+    own_row_load<T, D, EARLY, 1>(own, diag, b, x, nullptr, row, ld, MODE == 1, true);
+    const T dg = own.dg;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        const T ax = row_ax(acc[c], dg, x[row + (int64_t)c * ld]);
-        y[YI ? (int64_t)row * D + c : row + (int64_t)c * ld] = MODE == 1 ? b[row + (int64_t)c * ld] - ax : ax;
+        const T ax = row_ax(acc[c], dg, own.x[c]);
+        y[YI ? (int64_t)row * D + c : row + (int64_t)c * ld] = MODE == 1 ? own.b[c] - ax : ax;
     }
 }
 template <class T, int D, int MODE, int LPR, int C16 = 0, int YI = 0>
@@ -1292,18 +1351,29 @@ __device__ __forceinline__ void transfer_slice(const int64_t* __restrict__ slice
     const int lane = threadIdx.x & 63;
     const int srow = s * (64 / LPR) + lane / LPR;
     T acc[D];
+    // ADD = 1 is a read-modify-write of y: only safe when every output row is produced by exactly one slice row, so that
+    // instantiation never takes an output-row map (slice row == output row: unique by construction)
+    // The row's own operands in front of the dot (own_row_load): the y that a prolongation adds to (its `x` operand), the diagonal of the zero
+    // step -- and with it the output-row map entry its address needs, which the store waited for behind the dot as well.
+    constexpr int EARLY = OwnEarly<D>::value;
+    const bool mine = LPR == 1 || (lane & 3) == 0;                   // quad layout: the lane that stores
+    int row = srow;
+    OwnRow<T, D> own;
+    own.dg = (T)1;
+    if (EARLY != 0 && mine) {
+        if (!ADD && row_of) row = row_of[srow];
+        if (row >= 0) own_row_load<T, D, EARLY, 0>(own, diag0, nullptr, y, nullptr, row, ldy, false, ADD != 0, STEP0 != 0);
+    }
     // (quad layout = restrictions: a lane holds 4-5 of a row's ~18 entries -- one group of 8 in flight instead of 4 + a dependent tail)
     row_dot_sel<T, D, C16, (LPR == 4 ? 8 : DotGroup<D>::value), XI>(slice_ptr, col, col16, win_base, c16_arg, val, x, ldx, s, lane, acc);
     if (LPR == 4) { quad_reduce<T, D>(acc); if (lane & 3) return; }
-    // ADD = 1 is a read-modify-write of y: only safe when every output row is produced by exactly one slice row, so that
-    // instantiation never takes an output-row map (slice row == output row: unique by construction)
-    const int row = (!ADD && row_of) ? row_of[srow] : srow;
+    if (EARLY == 0 && !ADD && row_of) row = row_of[srow];
     if (row < 0) return;
-    T dg0 = (T)1;
-    if constexpr (STEP0 != 0) dg0 = diag0[row];
+    own_row_load<T, D, EARLY, 1>(own, diag0, nullptr, y, nullptr, row, ldy, false, ADD != 0, STEP0 != 0);
+    const T dg0 = own.dg;
 #pragma unroll
     for (int c = 0; c < D; ++c) {
-        if (ADD) y[row + (int64_t)c * ldy] += acc[c];
+        if (ADD) y[row + (int64_t)c * ldy] = own.x[c] + acc[c];
         else y[row + (int64_t)c * ldy] = acc[c];
         if constexpr (STEP0 != 0) {
             const T v = zero_step_row(acc[c], dg0, c0);
@@ -1830,15 +1900,19 @@ __global__ __launch_bounds__(kNormWaves * 64, 8) void residual_norm_slices(const
     if (s < n_slices) {
         const int row = s * 64 + lane;
         double acc[D];
+        constexpr int EARLY = OwnEarly<D>::value;
+        OwnRow<double, D> own;
+        own_row_load<double, D, EARLY, 0>(own, diag, b, x, weight, row, ld, true, true);
         row_dot_sel<double, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
-        const double dg = diag[row];
-        const double w = weight ? weight[row] : 1.0;
+        own_row_load<double, D, EARLY, 1>(own, diag, b, x, weight, row, ld, true, true);
+        const double dg = own.dg;
+        const double w = own.w;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-            const double bi = b[row + (int64_t)c * ld];
+            const double bi = own.b[c];
             double r;
-            if (MODE == 1) { r = bi - row_ax(acc[c], dg, x[row + (int64_t)c * ld]); r32[row + (int64_t)c * ld] = (float)r; }
-            else r = row_ax(acc[c], dg, x[row + (int64_t)c * ld]) - bi;
+            if (MODE == 1) { r = bi - row_ax(acc[c], dg, own.x[c]); r32[row + (int64_t)c * ld] = (float)r; }
+            else r = row_ax(acc[c], dg, own.x[c]) - bi;
             sums[2 * c] = norm_term(r, w);
             sums[2 * c + 1] = norm_term(bi, w);
         }
@@ -1869,15 +1943,19 @@ __global__ __launch_bounds__(kNormWaves * 64, 8) void residual_norm_slices_head(
     if (s < n_slices) {
         const int row = s * 64 + lane;
         double acc[D];
+        constexpr int EARLY = OwnEarly<D>::value;
+        OwnRow<double, D> own;
+        own_row_load<double, D, EARLY, 0>(own, diag, b, x, weight, row, ld, true, true);
         row_dot_sel<double, D, C16>(slice_ptr, col, col16, win_base, c16_arg, val, x, ld, s, lane, acc);
-        const double dg = diag[row];
-        const double w = weight ? weight[row] : 1.0;
+        own_row_load<double, D, EARLY, 1>(own, diag, b, x, weight, row, ld, true, true);
+        const double dg = own.dg;
+        const double w = own.w;
         const bool head = s >= hb && s < he;                               // wave-uniform
         const int64_t hrows = (int64_t)(he - hb) * 64;
 #pragma unroll
         for (int c = 0; c < D; ++c) {
-            const double bi = b[row + (int64_t)c * ld];
-            const double xi = x[row + (int64_t)c * ld];
+            const double bi = own.b[c];
+            const double xi = own.x[c];
             const double r = row_ax(acc[c], dg, xi) - bi;
             sums[2 * c] = norm_term(r, w);
             sums[2 * c + 1] = norm_term(bi, w);
