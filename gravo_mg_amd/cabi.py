@@ -44,7 +44,7 @@ class GmgConfig(C.Structure):
         ("row_align", C.c_int), ("block_rows", C.c_int), ("block_lanes", C.c_int), ("block_from_level", C.c_int),
         ("device_setup", C.c_int), ("device_rap", C.c_int), ("reorder_fine", C.c_int), ("inner_precision", C.c_int), ("block_csr", C.c_int), ("host_threads", C.c_int),
         ("verbose", C.c_int), ("gs_omega", C.c_double), ("restrict_sigma", C.c_int), ("block_ep", C.c_int), ("dist_shard_levels", C.c_int), ("block_fine", C.c_int), ("fine_col16", C.c_int), ("stream_gate", C.c_int), ("dist_exchange", C.c_int), ("prepare_structure", C.c_int), ("fuse_restrict_sweep", C.c_int), ("speculate_head", C.c_int), ("uniform_slices", C.c_int), ("color_ahead", C.c_int),
-        ("fold_head", C.c_int), ("reorder_pointwise", C.c_int), ("zero_guess_step", C.c_int), ("pcg", C.c_int), ("device_coloring", C.c_int), ("accelerate", C.c_int),
+        ("nullspace", C.c_int), ("fold_head", C.c_int), ("reorder_pointwise", C.c_int), ("zero_guess_step", C.c_int), ("pcg", C.c_int), ("device_coloring", C.c_int), ("accelerate", C.c_int),
     ]
 
 
@@ -173,6 +173,8 @@ INTERNAL_SIGNATURES = {
     "gmg_p2p_bench_kind": (C.c_int, [_vp, C.c_char_p, C.c_int, _dp]),
     "gmg_p2p_debug_collective_roundtrip": (C.c_int, [_vp, _dp, C.POINTER(C.c_longlong)]),
     "gmg_host_ldlt_probe": (C.c_int, [C.c_int, _ip, _ip, _dp, _dp, C.c_int, C.c_char_p, C.c_int]),
+    "gmg_host_nullspace_rowsum": (C.c_int, [C.c_int, _ip, _ip, _dp, C.c_int, _dp]),
+    "gmg_host_pinv_solve": (C.c_int, [C.c_int, _ip, _ip, _dp, _dp, C.c_int, _dp, _dp]),
 }
 
 _lib = None
@@ -354,7 +356,7 @@ class Engine:
 
     def __init__(self, smoother=SMOOTHER_MULTICOLOR_GS, pre_iters=2, post_iters=2, jacobi_omega=0.67,
                  coarse_mode=COARSE_AUTO, use_graph=False, sigma=0, row_align=64, block_rows=64, block_from_level=1, block_lanes=0,
-                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None, device_coloring=None, pcg=0, reorder_pointwise=None, zero_guess_step=None):
+                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None, device_coloring=None, pcg=0, reorder_pointwise=None, zero_guess_step=None, nullspace=0):
         l = lib()
         cfg = GmgConfig()
         l.gmg_config_default(C.byref(cfg))
@@ -399,6 +401,7 @@ class Engine:
             cfg.reorder_pointwise = int(reorder_pointwise)   # 0 / 1: reorder_fine applies to a pointwise smoother too (gmg_config::reorder_pointwise)
         if zero_guess_step is not None:
             cfg.zero_guess_step = int(zero_guess_step)       # 0 / 1: a pointwise smoother's first step on a zero guess is c * b / diag (gmg_config::zero_guess_step)
+        cfg.nullspace = int(nullspace)            # 0: positive definite systems; 1: semi-definite with the null space span{1} (gmg_config::nullspace)
         cfg.pcg = int(pcg)                        # 0: the plain loop; 1: CG preconditioned by the (symmetric) V-cycle (gmg_config::pcg)
         self._h = _vp()
         rc = l.gmg_create(C.byref(cfg), C.byref(self._h))
@@ -1081,6 +1084,29 @@ def host_ldlt_solve(A, b):
     if rc:
         raise GmgError(rc, "gmg_host_ldlt_solve (zero pivot?)")
     return (X[:, 0].copy() if np.asarray(b).ndim == 1 else X), nnz.value
+
+
+def host_nullspace_rowsum(A, coarsest: bool = False) -> Tuple[int, float]:
+    """(status, figure) of the row-sum rule of gmg_config::nullspace = 1 on A: max_i |sum_j a_ij| / sum_j |a_ij| against 1e-9.  The status is
+    what gmg_set_system returns for such a level 0 (GMG_ERR_INVALID) or coarsest operator (GMG_ERR_NUMERIC), GMG_OK within the bound."""
+    a = _csc(A)
+    out = C.c_double()
+    rc = lib().gmg_host_nullspace_rowsum(a.shape[0], _pi(a.indptr), _pi(a.indices), _pd(a.data), int(bool(coarsest)), C.byref(out))
+    return int(rc), out.value
+
+
+def host_pinv_solve(A, b):
+    """x = A^+ b for a symmetric positive semi-definite A with null space span{1}, as GMG_COARSE_HOST_LDLT applies it on a nullspace = 1
+    handle: the coarsest solver's factor with its last pivot pinned, between two mean removals.  Returns (x, (row-sum figure, replaced pivot /
+    largest pivot)); raises GmgError (GMG_ERR_NUMERIC) when the rows do not sum to zero or a pivot before the last one is zero."""
+    a = _csc(A)
+    B = _f64(b)
+    X = np.empty_like(B, order="F")
+    info = np.zeros(2)
+    rc = lib().gmg_host_pinv_solve(a.shape[0], _pi(a.indptr), _pi(a.indices), _pd(a.data), _pd(B), B.shape[1], _pd(X), _pd(info))
+    if rc:
+        raise GmgError(rc, f"gmg_host_pinv_solve (row sums {info[0]:.3e}; zero pivot before the last one?)")
+    return (X[:, 0].copy() if np.asarray(b).ndim == 1 else X), (float(info[0]), float(info[1]))
 
 
 def host_ldlt_probe(A, b, reps: int = 3) -> str:

@@ -342,6 +342,7 @@ public:
         else if (key == "pcg") c.pcg = (int)value;
         else if (key == "reorder_pointwise") c.reorder_pointwise = (int)value;
         else if (key == "zero_guess_step") c.zero_guess_step = (int)value;
+        else if (key == "nullspace") c.nullspace = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

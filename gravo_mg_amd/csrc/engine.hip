@@ -50,6 +50,7 @@
 #include "hierarchy_kernels.hip.hpp"
 #include "accel_kernels.hip.hpp"
 #include "pcg_kernels.hip.hpp"
+#include "nullspace_kernels.hip.hpp"
 
 using namespace gmg;
 using clk = std::chrono::steady_clock;
@@ -138,6 +139,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->prepare_structure = 1;
     cfg->fuse_restrict_sweep = 1;
     cfg->speculate_head = 1;
+    cfg->nullspace = 0;       // symmetric positive definite systems (1: semi-definite with the null space span{1}, see gmg_config)
     cfg->fold_head = 1;
     cfg->uniform_slices = 1;
     cfg->color_ahead = 1;
@@ -171,6 +173,7 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     create_error().clear();
     gmg_config c;
     if (cfg) c = *cfg; else gmg_config_default(&c);
+    if (c.nullspace < 0 || c.nullspace > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::nullspace must be 0 or 1");
     if (c.sigma < 0 || c.sigma % 64 || c.restrict_sigma < 0 || c.restrict_sigma % 64 || c.row_align <= 0 || c.row_align % 64 || c.pre_iters < 0 || c.post_iters < 0 ||
         c.reorder_fine < 0 || c.reorder_fine > 2 || c.inner_precision < 0 || c.inner_precision > 1 || c.block_rows < 0 || c.block_rows > gmgk::kBlockRows || c.block_rows % 64 || c.block_from_level < 0 || !(c.gs_omega > 0.0 && c.gs_omega < 2.0) || c.dist_shard_levels < 1 || c.dist_shard_levels > 2 || c.block_fine < 0 || c.block_fine > 1 || c.dist_exchange < 0 || c.dist_exchange > 2 ||
         (c.block_lanes != 0 && c.block_lanes != 1 && c.block_lanes != 4) || (c.block_lanes != 1 && c.block_rows > gmgk::kQuadBlockRows)) return GMG_ERR_INVALID;
@@ -190,6 +193,7 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
     }
     gmg_handle h = new gmg_solver_s();
     h->cfg = c;
+    h->coarse.pin_last = c.nullspace != 0;      // the coarsest factor takes its last pivot for what it is (host_ldlt.hpp)
     if (h->cfg.host_threads <= 0) h->cfg.host_threads = hw_threads();
     int ndev = gmg_device_count();
     if (ndev > 0 && c.device >= 0 && c.device < ndev && hipSetDevice(c.device) == hipSuccess &&
@@ -852,6 +856,14 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     auto t_all = clk::now();
     HelperScope helper_scope(h, d);
     if ((rc = load())) return rc;
+    // gmg_config::nullspace = 1: b <- b - (1^T b / n) 1, the orthogonal projection onto range(A); everything behind this line -- the three
+    // loops, their residual checks -- sees the projected right-hand side (the fp32 inner cycle's first defect is formed again from it)
+    const int nullspace = h->cfg.nullspace;
+    if (nullspace) {
+        if ((rc = ensure_nullspace(h))) return rc;
+        launch_nullspace_project(h, d, h->lv[0].b, nullptr, 0);
+        if (h->cfg.inner_precision && (rc = launch_residual_to_f32(h, d, -1))) return rc;
+    }
     h->timing["solve_load"] = ms_since(t_all);
     h->timing["coarse_host_ms"] = 0.0;
     auto t0 = clk::now();
@@ -968,6 +980,21 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     h->timing["accel_guard_steps"] = guard_steps;
+    if (nullspace) {
+        // x <- x - (m^T x / m^T 1) 1: the solution of zero mass-weighted mean (unit weights without a mass); A 1 = 0 leaves the residue as reported
+        launch_nullspace_project(h, d, l0.x, h->d_mass ? h->d_mass.get() : nullptr, 1);
+        std::vector<double> sums((size_t)6 * h->nullsp.d, 0.0);
+        HIPCHK(hipMemcpyAsync(sums.data(), h->nullsp.scal, sizeof(double) * sums.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        // max over the columns of |1^T b| / (sqrt(n) |b|_2) before the projection (a zero column counts 0)
+        double defect = 0.0;
+        const int DA = h->nullsp.d;
+        for (int c = 0; c < d; ++c) {
+            const double s1 = sums[(size_t)DA + c], s2 = sums[(size_t)2 * DA + c];
+            if (s2 > 0.0) defect = std::max(defect, std::fabs(s1) / (std::sqrt((double)l0.n) * std::sqrt(s2)));
+        }
+        h->timing["nullspace_rhs_defect"] = defect;
+    }
     auto t_f = clk::now();
     if ((rc = fetch())) return rc;
     h->timing["solve_fetch"] = ms_since(t_f);
@@ -1077,6 +1104,7 @@ int gmg_dist_partition(gmg_handle h, int rank, int world) try {
     PoolScope pool_scope_(&h->pool);
     if (world < 1 || rank < 0 || rank >= world) return fail(h, GMG_ERR_INVALID, "bad rank / world size");
     if (world > 1 && h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only (create the handle with accelerate = 0)");
+    if (world > 1 && h->cfg.nullspace) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::nullspace runs on one device only (create the handle with nullspace = 0)");
     if (world > 1 && h->cfg.row_align % (64 * world)) return fail(h, GMG_ERR_STATE, "create the handle with row_align = 64 * world (colour classes are cut into `world` pieces of whole slices)");
     if (rank == h->part_rank && world == h->part_world) return GMG_OK;
     if (h->has_device && h->live != LiveSystem::none) { drop_system(h); h->live_key_valid = false; }      // laid out for another partition
@@ -1091,6 +1119,7 @@ int gmg_dist_setup(gmg_handle h, int rank, int world) try {
     if (rc) return rc;
     if (world < 1 || rank < 0 || rank >= world) return fail(h, GMG_ERR_INVALID, "bad rank / world size");
     if (world > 1 && h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only (create the handle with accelerate = 0)");
+    if (world > 1 && h->cfg.nullspace) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::nullspace runs on one device only (create the handle with nullspace = 0)");
     if (h->partitioned && (rank != h->part_rank || world != h->part_world)) return fail(h, GMG_ERR_STATE, "the system was laid out for another rank / world size (gmg_dist_partition)");
     const LevelOrdering& o = h->lv[0].ord;
     if (h->cfg.smoother != GMG_SMOOTHER_MULTICOLOR_GS) return fail(h, GMG_ERR_STATE, std::string("the distributed path needs the multicolour / block-hybrid smoothers (gmg_config::smoother), this handle runs ") + smoother_name(h->cfg));
@@ -1878,6 +1907,41 @@ int gmg_host_ldlt_solve(int n, const int* colptr, const int* rowidx, const doubl
     std::vector<double> w((size_t)n * d);
     f.solve_multi(b, (size_t)n, x, (size_t)n, d, w.data());
     if (factor_nnz) *factor_nnz = f.factor_nnz();
+    return GMG_OK;
+} GMG_CATCH_0
+
+// Host-only views of gmg_config::nullspace = 1 (gravomg_hip_internal.h): the set-up's row-sum rule, and the pinned factor between two mean removals
+static int csc_fault(int n, const int* colptr, const int* rowidx) {
+    if (colptr[0] != 0) return 1;
+    for (int i = 0; i < n; ++i) if (colptr[i + 1] < colptr[i]) return 1;
+    for (int q = 0; q < colptr[n]; ++q) if (rowidx[q] < 0 || rowidx[q] >= n) return 1;
+    return 0;
+}
+int gmg_host_nullspace_rowsum(int n, const int* colptr, const int* rowidx, const double* val, int coarsest, double* rowsum) try {
+    if (n <= 0 || !colptr || !rowidx || !val || csc_fault(n, colptr, rowidx)) return GMG_ERR_INVALID;
+    Compressed A;
+    A.assign(n, n, colptr, rowidx, val);
+    const double worst = nullspace_rowsum(A);
+    if (rowsum) *rowsum = worst;
+    if (worst <= kNullspaceRowsumMax) return GMG_OK;
+    return coarsest ? GMG_ERR_NUMERIC : GMG_ERR_INVALID;
+} GMG_CATCH_0
+
+int gmg_host_pinv_solve(int n, const int* colptr, const int* rowidx, const double* val, const double* b, int d, double* x, double* info) try {
+    if (n <= 0 || !colptr || !rowidx || !val || !b || !x || d <= 0 || csc_fault(n, colptr, rowidx)) return GMG_ERR_INVALID;
+    Compressed A;
+    A.assign(n, n, colptr, rowidx, val);
+    const double worst = nullspace_rowsum(A);
+    if (info) { info[0] = worst; info[1] = 0.0; }
+    if (!(worst <= kNullspaceRowsumMax)) return GMG_ERR_NUMERIC;
+    SupernodalLDLT f;
+    f.pin_last = true;
+    if (!f.factor(A)) return GMG_ERR_NUMERIC;
+    if (info) info[1] = f.pinned_pivot;
+    std::vector<double> rhs(b, b + (size_t)n * d), w((size_t)n * d);
+    remove_means(rhs.data(), (size_t)n, n, d);
+    f.solve_multi(rhs.data(), (size_t)n, x, (size_t)n, d, w.data());
+    remove_means(x, (size_t)n, n, d);
     return GMG_OK;
 } GMG_CATCH_0
 

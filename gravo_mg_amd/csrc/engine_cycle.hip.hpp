@@ -643,6 +643,7 @@ int ensure_vectors(gmg_handle h, int d) {
     unbind_level0(h);
     h->accel = {};
     h->pcg = {};
+    h->nullsp = {};
     // a zeroed n_pad x d vector of the level, or none (wanted = false): the old one goes back to the pool either way
     auto vec = [&](auto& v, const Level& l, bool wanted) -> int {
         v.reset();
@@ -1018,7 +1019,11 @@ void coarse_host_solve(gmg_handle h, int d) {
     auto t0 = clk::now();
     std::memset(e, 0, sizeof(double) * cnt);
     if (h->coarse_work.size() < (size_t)c.n * d) h->coarse_work.resize((size_t)c.n * d);
+    // gmg_config::nullspace = 1: the pinned factor applies G; with the means removed on both sides this is P G P = A_L^+, the operator the
+    // device modes keep as a matrix
+    if (h->cfg.nullspace) remove_means(rc, (size_t)c.n_pad, c.n, d);
     h->coarse.solve_multi(rc, (size_t)c.n_pad, e, (size_t)c.n_pad, d, h->coarse_work.data(), h->coarse_helper.get());
+    if (h->cfg.nullspace) remove_means(e, (size_t)c.n_pad, c.n, d);
     h->timing["coarse_host_ms"] += ms_since(t0);
 }
 
@@ -1341,6 +1346,36 @@ int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
     });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
+}
+
+// ---- the projections of a solve on a semi-definite system (gmg_config::nullspace; engine.hip::solve_common; kernels: nullspace_kernels.hip.hpp) ----
+
+int ensure_nullspace(gmg_handle h) {
+    auto& a = h->nullsp;
+    const int D = h->dcap;
+    if (a.scal && a.d == D) return GMG_OK;
+    a = {};
+    int rc;
+    if ((rc = dev_alloc(h, a.partials, (size_t)gmgk::kAccelMaxBlocks * 9)) || (rc = dev_alloc(h, a.scal, (size_t)6 * D))) return rc;
+    a.d = D;
+    return GMG_OK;
+}
+
+// v <- v - (w^T v / w^T 1) 1 on the real rows of a level-0 vector (n_pad x d), column by column; w == nullptr: unit weights.  slot 0: the
+// right-hand side, 1: the iterate -- where nullspace_reduce leaves the shifts and the sums (NullspaceState::scal).
+void launch_nullspace_project(gmg_handle h, int d, double* v, const double* w, int slot) {
+    auto& a = h->nullsp;
+    Level& l = h->lv[0];
+    const int DA = a.d, ld = l.n_pad, n_pairs = l.n_pad / 2;
+    const int nblk = std::max(1, std::min(gmgk::kAccelMaxBlocks, (n_pairs + gmgk::kAccelBlock - 1) / gmgk::kAccelBlock));
+    double* out = a.scal + (size_t)slot * 3 * DA;
+    const int* real = l.d_new2old;
+    for_col_chunks(d, [&](int c0, int dc) {
+        double* vc = v + (size_t)c0 * ld;
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::nullspace_sums<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, (const double*)vc, w, real, ld, n_pairs, a.partials.get()));
+        hipLaunchKernelGGL(gmgk::nullspace_reduce, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, (const double*)a.partials, nblk, dc, DA, out + c0);
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::nullspace_shift<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, vc, (const double*)(out + c0), real, ld, n_pairs));
+    });
 }
 
 // ---- the solve loop (gmg_solve, gmg_solve_x0_rhs, gmg_solve_device, gmg_p2p_solve) -----------------------------------------------------

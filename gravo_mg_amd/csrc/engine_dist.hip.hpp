@@ -368,6 +368,7 @@ int gmg_p2p_prepare(gmg_handle h, int rank, int world, int d) try {
     if (rc) return rc;
     if (world < 1 || rank < 0 || rank >= world || d < 1 || d > 4) return fail(h, GMG_ERR_INVALID, "bad rank / world size / column count (d <= 4)");
     if (h->cfg.accelerate > 0) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::accelerate runs on one device only: the multi-rank cycle is not accelerated (create the handle with accelerate = 0)");
+    if (h->cfg.nullspace) return fail(h, GMG_ERR_UNSUPPORTED, "gmg_config::nullspace runs on one device only: the multi-rank cycle projects nothing (create the handle with nullspace = 0)");
     if ((rc = gmg_dist_setup(h, rank, world))) return rc;
     p2p_release(h);
     if ((rc = ensure_vectors(h, d))) return rc;

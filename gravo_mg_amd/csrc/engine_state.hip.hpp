@@ -270,6 +270,14 @@ struct gmg_solver_s {
         int d = 0, n_pad = 0;
         bool exchanged = false;
     } pcg;
+    // The two projections of a solve on a gmg_config::nullspace = 1 handle (engine.hip::solve_common; nullspace_kernels.hip.hpp): the partial sums
+    // of nullspace_sums and, per column, what nullspace_reduce leaves -- the shift, sum w v and sum v^2 -- once for the right-hand side and once
+    // for the iterate.  Allocated by the first such solve (ensure_nullspace), released with the level vectors like accel and pcg.
+    struct NullspaceState {
+        DevBuf<double> partials;         // kAccelMaxBlocks x 9
+        DevBuf<double> scal;             // 2 x 3 d doubles: {shift[d], sum w v[d], sum v^2[d]} of the right-hand side, then of the iterate
+        int d = 0;
+    } nullsp;
     // Head of the next cycle (gmg_config::speculate_head; engine.hip::solve_common): the solve loop's decision is taken by the check's
     // reduction on the device (d_watch: {double least; int go}), the first colour launch of the next cycle is enqueued behind it before the
     // host has seen the norm, and returns at once when the iteration stopped.  Only the device words live here: what the reduction needs to
@@ -590,6 +598,7 @@ void drop_system(gmg_handle h) {
     unbind_level0(h);
     h->accel = {};
     h->pcg = {};
+    h->nullsp = {};
     h->dist_ready = false;
     h->lv.clear();
     h->dcap = 0;

@@ -134,7 +134,9 @@ bool want_coarse_triangle(gmg_handle h) { return h->cfg.coarse_mode == GMG_COARS
 // runs this on a caller's matrix.
 enum { kInvFollowPermute = 0, kInvFollowScatter = 1, kInvFollowTriangle = 2, kInvFollowMirror = 3 };
 struct CoarseInverseRun { double upload_ms = 0.0; float tiles_ms = 0.f; bool timed = false; };
-int coarse_inverse_core(gmg_handle h, const SupernodalLDLT::DeviceFactor& E, int width, int follow, DevBuf<double>& X, double* dst, int ldo, CoarseInverseRun& run) {
+// center (gmg_config::nullspace = 1, a factor with its last pivot pinned): the triangle the tiles computed is double-centred before the follow-up
+// kernels run (gmgs::inverse_col_sums, gmgs::inverse_center): what they mirror, permute or pack is then the pseudo-inverse.
+int coarse_inverse_core(gmg_handle h, const SupernodalLDLT::DeviceFactor& E, int width, int follow, DevBuf<double>& X, double* dst, int ldo, CoarseInverseRun& run, bool center = false) {
     auto t0 = clk::now();
     const int nl = E.n;
     std::vector<int> tile_ptr_h, tile_q_h;
@@ -159,6 +161,8 @@ int coarse_inverse_core(gmg_handle h, const SupernodalLDLT::DeviceFactor& E, int
     if (permuted && ((rc = upload(h, perm_d, E.perm)) || (rc = upload(h, inv_d, inv_h)))) return rc;
     const size_t bytes = sizeof(double) * (size_t)nl * nl;
     if ((rc = dev_alloc(h, X, (size_t)nl * nl))) return rc;
+    DevBuf<double> col_sums;
+    if (center && nl > 0 && (rc = dev_alloc(h, col_sums, (size_t)nl))) return rc;
     HIPCHK(hipMemsetAsync(X, 0, bytes, h->stream));
     gmgs::InvFactor F;
     F.n = nl; F.nq = E.nq; F.nlev = E.nlev;
@@ -175,6 +179,10 @@ int coarse_inverse_core(gmg_handle h, const SupernodalLDLT::DeviceFactor& E, int
         else if (width == 32) hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<32>, dim3(nt), block, 0, h->stream, F, X.get());
         else hipLaunchKernelGGL(gmgs::coarse_inverse_tiles<64>, dim3(nt), block, 0, h->stream, F, X.get());
         (void)hipEventRecord(h->ev1, h->stream);
+        if (center) {
+            hipLaunchKernelGGL(gmgs::inverse_col_sums, dim3(nm), dim3(gmgs::kCenterBlock), 0, h->stream, (const double*)X, nl, col_sums.get());
+            hipLaunchKernelGGL(gmgs::inverse_center, dim3(nm, nm), dim3(gmgs::kCenterBlock), 0, h->stream, X.get(), nl, (const double*)col_sums);
+        }
         if (follow == kInvFollowTriangle) {
             hipLaunchKernelGGL(gmgs::pack_lower_blocks, dim3(nb, nb), dim3(256), 0, h->stream, (const double*)X, nl, dst);
         } else {
@@ -229,7 +237,7 @@ int build_coarse_inverse_device(gmg_handle h) {
     CoarseInverseRun run;
     const int follow = tri_mode ? kInvFollowTriangle : (nl <= kInvPermuteLdsMax ? kInvFollowPermute : kInvFollowScatter);
     const double before = ms_since(t0);
-    if ((rc = coarse_inverse_core(h, E, width, follow, X, tri_mode ? h->d_tri.get() : h->d_ainv.get(), lda, run))) return rc;
+    if ((rc = coarse_inverse_core(h, E, width, follow, X, tri_mode ? h->d_tri.get() : h->d_ainv.get(), lda, run, h->cfg.nullspace != 0))) return rc;
     h->timing["coarse_inverse_upload_ms"] = before + run.upload_ms - h->timing["coarse_inverse_export_ms"];
     if (run.timed) h->timing["coarse_inverse_tiles_ms"] = run.tiles_ms;
     h->timing["coarse_inverse_ms"] = ms_since(t0);
@@ -294,12 +302,41 @@ int compute_cheby_bounds(gmg_handle h) {
     return GMG_OK;
 }
 
+// gmg_config::nullspace = 1: the claim is checked on every set-up with real values.  Level 0: max_i |sum_j a_ij| / sum_j |a_ij|
+// from the resident layout (gmgs::rowsum_rows + its reduction, one double read back); the coarsest operator: the same figure on the host,
+// from the matrix the factorisation read.  Timing keys "nullspace", "nullspace_rowsum_l0", "nullspace_rowsum_coarse", "nullspace_pinned_pivot".
+int check_nullspace_claim(gmg_handle h) {
+    const int L = h->L;
+    const Level& l = h->lv[0];
+    if (l.Aoff.lpr != 1 || !l.Aoff.slice_ptr || !l.diag || !l.d_new2old) return fail(h, GMG_ERR_STATE, "gmg_config::nullspace needs the one-lane-per-row operator layout of level 0");
+    constexpr int per_block = gmgs::kGershBlock / 64;
+    const int nblk = (l.Aoff.n_slices + per_block - 1) / per_block;
+    DevBuf<double> partials, worst;
+    int rc;
+    if ((rc = dev_alloc(h, partials, (size_t)std::max(nblk, 1))) || (rc = dev_alloc(h, worst, 1))) return rc;
+    if (nblk > 0) hipLaunchKernelGGL(gmgs::rowsum_rows<double>, dim3(nblk), dim3(gmgs::kGershBlock), 0, h->stream, l.Aoff.slice_ptr, (const double*)l.Aoff.val,
+                                     (const double*)l.diag, (const int*)l.d_new2old, l.Aoff.n_slices, partials.get());
+    hipLaunchKernelGGL(gmgs::rowsum_reduce, dim3(1), dim3(gmgs::kGershBlock), 0, h->stream, (const double*)partials, nblk, worst.get());
+    double rowsum0 = 0.0;
+    HIPCHK(hipMemcpyAsync(&rowsum0, worst, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const double rowsum_c = nullspace_rowsum(h->lv[L].A);          // (beside the device's work)
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->timing["nullspace"] = 1.0;
+    h->timing["nullspace_rowsum_l0"] = rowsum0;
+    h->timing["nullspace_rowsum_coarse"] = rowsum_c;
+    h->timing["nullspace_pinned_pivot"] = h->coarse.pinned_pivot;
+    if (!(rowsum0 <= kNullspaceRowsumMax)) return fail(h, GMG_ERR_INVALID, "nullspace = 1 but A 1 != 0 (largest |row sum| / sum of |entries| on level 0: " + std::to_string(rowsum0) + ")");
+    if (!(rowsum_c <= kNullspaceRowsumMax)) return fail(h, GMG_ERR_NUMERIC, "nullspace = 1 but the prolongations do not preserve constants (largest |row sum| / sum of |entries| of the coarsest operator: " + std::to_string(rowsum_c) + ")");
+    return GMG_OK;
+}
+
 // The end of every set-up: where the coarsest solve runs (+ its dense inverse unless inverse_ready), the fp32 twins, the mass -- when it
 // changed or has no device copy (after the drop_system of a full set-up: always), and not for placeholder values.
 int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, bool alloc_twins, bool placeholder) {
     const int L = h->L;
     int rc;
     h->timing["coarsest_solve"] = ms_factor;
+    if (h->cfg.nullspace && !placeholder && (rc = check_nullspace_claim(h))) return rc;      // (before anything is built on the claim)
     h->timing["fine_level_reordered"] = h->lv[0].ord.reordered ? 1.0 : 0.0;      // level 0 follows a locality order (reorder_fine; gmg_config::reorder_pointwise)
     h->coarse_device = want_coarse_device(h, h->lv[L].A.n_outer);
     h->timing["coarse_on_device"] = h->coarse_device ? 1.0 : 0.0;

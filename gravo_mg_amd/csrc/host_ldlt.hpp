@@ -15,6 +15,7 @@
 #include <condition_variable>
 #include <cstdint>
 #include <iterator>
+#include <limits>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -515,6 +516,13 @@ public:
     std::vector<int> perm;              // new -> old
 
     double phase_ms[3] = {0, 0, 0};     // ordering / symbolic / numeric of the last factor() (measurement aid)
+    // "pin the last pivot" (gmg_config::nullspace = 1: A is positive SEMI-definite with the null space span{1}): the last pivot in
+    // elimination order -- rounding noise, A_L 1 = 0 -- is accepted whatever it is (zero, tiny, negative) and replaced so that 1 / D = 0; every
+    // earlier pivot keeps the test of panel_factor.  solve*, emulate_device_column and DeviceFactor::dinv then apply G = [[A11^-1, 0], [0, 0]]
+    // (the pinned unknown last), and P G P with P = I - 1 1^T / n is the pseudo-inverse.  pinned_pivot: the replaced pivot over the largest
+    // pivot in magnitude, after a factor() in this mode.
+    bool pin_last = false;
+    double pinned_pivot = 0.0;
     bool factor(const Compressed& A, bool reuse_perm = false) {
         using clk = std::chrono::steady_clock;
         auto ms = [](clk::time_point a) { return std::chrono::duration<double, std::milli>(clk::now() - a).count(); };
@@ -928,6 +936,7 @@ private:
     };
     PanelStore pan_;
     std::vector<double> D_;
+    double pinned_raw_ = 0.0;                    // pin_last: what the last pivot would have been
 
     // upper triangle of P A P^T by columns (row indices only) + elimination tree + column counts of L
     void upper_and_etree(const Compressed& A, std::vector<int>& parent, std::vector<int>& lnz, bool counts = true) {
@@ -1530,7 +1539,23 @@ private:
         const int f = sn_first_[s], w = sn_first_[s + 1] - f;
         const int ld = w + (rows_ptr_[s + 1] - rows_ptr_[s]);
         double* P = pan_.data() + pan_ptr_[s];
-        return avx ? panel_factor_avx2(P, ld, ld, w, D_.data() + f) : panel_factor_base(P, ld, ld, w, D_.data() + f);
+        // pin_last: the supernode that ends with the last column of the elimination order factors the columns before it only (their rows reach
+        // down to that column's); the last pivot is taken for what it is and replaced (pin_last_pivot)
+        const bool pin = pin_last && f + w == n;
+        const int wf = pin ? w - 1 : w;
+        const bool fine = avx ? panel_factor_avx2(P, ld, ld, wf, D_.data() + f) : panel_factor_base(P, ld, ld, wf, D_.data() + f);
+        if (fine && pin) pin_last_pivot(P, ld, w, f);
+        return fine;
+    }
+    // The last column of the elimination order has nothing below its diagonal, so its column of L is the unit vector whatever its pivot is.
+    // What the pivot would have been (the panel's entry minus the updates of the panel's own earlier columns: those of the descendants are in
+    // it already) is kept for the report; D = +inf in its place makes both y / D of the back-substitutions and 1 / D of the exported factor
+    // an exact zero: the factor then solves with G = [[A11^-1, 0], [0, 0]].
+    void pin_last_pivot(const double* P, int ld, int w, int f) {
+        double piv = P[(size_t)(w - 1) * ld + (w - 1)];
+        for (int j = 0; j < w - 1; ++j) { const double l = P[(size_t)j * ld + (w - 1)]; piv -= l * l * D_[(size_t)f + j]; }
+        pinned_raw_ = piv;
+        D_[(size_t)n - 1] = std::numeric_limits<double>::infinity();
     }
     void numeric(const Compressed& A) {
         if (pan_.fresh) pan_.fresh = false;       // first factorisation into this storage: zero already, pages not yet touched
@@ -1643,6 +1668,11 @@ private:
         }
         if (trace) std::fprintf(stderr, "[gmg ldlt] top: %d supernodes, mean width %.1f, mean rows below %.1f, mean updates %.1f, products %.2f ms, subtraction %.2f ms, panel factor %.2f ms\n", n_top, w_sum / std::max(n_top, 1), r_sum / std::max(n_top, 1), u_sum / std::max(n_top, 1), t_prod, t_sub, t_fac);
         lap("top");
+        if (pin_last) {
+            double big = 0.0;
+            for (int j = 0; j + 1 < n; ++j) big = std::max(big, std::fabs(D_[(size_t)j]));
+            pinned_pivot = big > 0.0 ? pinned_raw_ / big : 0.0;
+        }
         ok = true;
     }
 
@@ -1662,5 +1692,34 @@ private:
     }
 
 };
+
+// ---- gmg_config::nullspace = 1: what the set-up checks and what GMG_COARSE_HOST_LDLT does around the pinned factor ------------
+// max_i |sum_j a_ij| / sum_j |a_ij| of a square matrix in compressed storage (rows found by scattering: no symmetry assumed; a row without a
+// nonzero entry counts 0).  A row holds fewer than 100 entries, so rounding stays below 100 eps = 2e-14; kNullspaceRowsumMax leaves five
+// orders of margin and still rejects S + 1e-6 M.
+constexpr double kNullspaceRowsumMax = 1e-9;
+inline double nullspace_rowsum(const Compressed& A) {
+    const int n = A.n_outer;
+    std::vector<double> sum((size_t)n, 0.0), mag((size_t)n, 0.0);
+    for (int j = 0; j < n; ++j)
+        for (int p = A.ptr[j]; p < A.ptr[j + 1]; ++p) { sum[(size_t)A.idx[p]] += A.val[p]; mag[(size_t)A.idx[p]] += std::fabs(A.val[p]); }
+    double worst = 0.0;
+    for (int i = 0; i < n; ++i) {
+        if (mag[(size_t)i] == 0.0) continue;
+        const double r = std::fabs(sum[(size_t)i]) / mag[(size_t)i];
+        if (!(r <= worst)) worst = r;          // (a NaN stays: the caller's `!(figure <= bound)` then refuses)
+    }
+    return worst;
+}
+// v <- v - mean(v) on n entries, column by column (the sum in index order)
+inline void remove_means(double* v, size_t ld, int n, int d) {
+    for (int c = 0; c < d; ++c) {
+        double* vc = v + (size_t)c * ld;
+        double s = 0.0;
+        for (int i = 0; i < n; ++i) s += vc[i];
+        const double mean = n > 0 ? s / n : 0.0;
+        for (int i = 0; i < n; ++i) vc[i] -= mean;
+    }
+}
 
 }  // namespace gmg

@@ -134,7 +134,10 @@ public:
     std::vector<std::tuple<double, double>> convergence;
 
     /* MI355X engine knobs (not in the reference).  engineConfig.pcg = 1 (with a pointwise smoother; preIters == postIters) makes solve() run
-       conjugate gradients preconditioned by the cycle; the exact Gauss-Seidel retry handle is always created with pcg = 0. */
+       conjugate gradients preconditioned by the cycle; the exact Gauss-Seidel retry handle is always created with pcg = 0.
+       engineConfig.nullspace = 1: solve() takes symmetric positive SEMI-definite systems whose null space is the constants (a stiffness matrix
+       or a Bilaplacian as it is): pseudo-inverse on the coarsest level, right-hand side projected onto the range, solution of zero
+       mass-weighted mean (gmg_config::nullspace); the retry handle keeps the field. */
     gmg_config engineConfig;
     /* Set by a caller that KNOWS the initial guess of the next solve() is the right-hand side (the binding: core.cpp:69): x is then
        output only -- it need not hold a copy of rhs -- and the engine copies rhs to x on the device (gmg_solve_x0_rhs). */

@@ -1047,6 +1047,138 @@ __global__ __launch_bounds__(kGershBlock) void gershgorin_reduce(const double* _
     }
 }
 
+// ---- gmg_config::nullspace = 1: the claim A 1 = 0 on level 0 -----------------------------------------------------------------
+// max_i |sum_j a_ij| / sum_j |a_ij| over the REAL rows of the resident level-0 layout (off-diagonal slices plus diagonal), in the form of
+// gershgorin_rows: one wave per 64-row slice, the wave's maximum by shuffles, the block's through LDS into partials[block]; rowsum_reduce (one
+// block) takes the maximum of the partials.  Padding rows (new2old < 0: an empty row with a unit diagonal) and rows without a nonzero entry
+// count 0; a figure that is not a number counts as infinity, so that the maximum cannot lose it.  A maximum does not depend on the order.
+template <class T>
+__global__ __launch_bounds__(kGershBlock) void rowsum_rows(const int64_t* __restrict__ slice_ptr, const T* __restrict__ val, const T* __restrict__ diag,
+                                                           const int* __restrict__ new2old, int n_slices, double* __restrict__ partials) {
+    __shared__ double red[kGershBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * (kGershBlock / 64) + wave;
+    double v = 0.0;
+    if (s < n_slices) {
+        const int64_t p0 = slice_ptr[s];
+        const int w = (int)((slice_ptr[s + 1] - p0) >> 6);
+        const T* vp = val + p0 + lane;
+        const int64_t row = (int64_t)s * 64 + lane;
+        double sum = (double)diag[row], mag = fabs(sum);
+        for (int j = 0; j < w; ++j) { const double a = (double)vp[(int64_t)j * 64]; sum += a; mag += fabs(a); }
+        if (new2old[row] >= 0 && mag != 0.0) {
+            v = fabs(sum) / mag;
+            if (!(v == v)) v = INFINITY;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < kGershBlock / 64; ++w2) m = fmax(m, red[w2]);
+        partials[blockIdx.x] = m;
+    }
+}
+
+__global__ __launch_bounds__(kGershBlock) void rowsum_reduce(const double* __restrict__ partials, int n, double* __restrict__ out) {
+    __shared__ double red[kGershBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double v = 0.0;
+    for (int i = threadIdx.x; i < n; i += kGershBlock) v = fmax(v, partials[i]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    if (lane == 0) red[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double m = red[0];
+#pragma unroll
+        for (int w2 = 1; w2 < kGershBlock / 64; ++w2) m = fmax(m, red[w2]);
+        *out = m;
+    }
+}
+
+// ---- gmg_config::nullspace = 1: double-centring of the device-built coarse inverse ---------------------------------------------
+// The tiles leave G = [[A11^-1, 0], [0, 0]] of the pinned factor in the lower triangle of X (n x n row-major, factor's numbering, rows j >= c
+// of column c); the pseudo-inverse is P G P with P = I - 1 1^T / n, entry (i, j): G_ij - (s_i + s_j) / n + mu with s the column sums of the
+// symmetric G and mu = sum(s) / n^2.  Centring commutes with the permutation, so it is done here, between the tiles and the kernels that
+// mirror / permute / pack (which run unchanged).  Two launches, every sum in one fixed order, no floating-point atomics.
+//
+// inverse_col_sums: s_j = sum_{i >= j} X_ij + sum_{i < j} X_ji.  One block per 64 columns j0 .. j0 + 63, four waves.  The column part reads
+// rows i >= j0 of the 64-column slab (a row of it = 64 consecutive doubles: coalesced), wave w the rows j0 + w, j0 + w + 4, ..., lane = column;
+// the row part of row j (contiguous) goes to wave (j - j0) % 4, lanes striding it, a shuffle tree at its end.  s_j = the four waves' column
+// sums in wave order, then the row part.  grid: ceil(n / 64).
+constexpr int kCenterBlock = 256;
+__global__ __launch_bounds__(kCenterBlock) void inverse_col_sums(const double* __restrict__ X, int n, double* __restrict__ s) {
+    __shared__ double col_part[kCenterBlock / 64][64];
+    __shared__ double row_part[64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int j0 = blockIdx.x * 64, j = j0 + lane;
+    double acc = 0.0;
+    if (j < n) {
+        // four rows in flight per wave (a row of the slab is one dependent trip to memory); four sums, added in one fixed order
+        constexpr int W = kCenterBlock / 64;
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+        int i = j0 + wave;
+        for (; i + 3 * W < n; i += 4 * W) {
+            const double v0 = i >= j ? X[(int64_t)i * n + j] : 0.0, v1 = i + W >= j ? X[(int64_t)(i + W) * n + j] : 0.0;
+            const double v2 = i + 2 * W >= j ? X[(int64_t)(i + 2 * W) * n + j] : 0.0, v3 = i + 3 * W >= j ? X[(int64_t)(i + 3 * W) * n + j] : 0.0;
+            a0 += v0; a1 += v1; a2 += v2; a3 += v3;
+        }
+        for (; i < n; i += W)
+            if (i >= j) a0 += X[(int64_t)i * n + j];
+        acc = (a0 + a1) + (a2 + a3);
+    }
+    col_part[wave][lane] = acc;
+    for (int r = wave; r < 64; r += kCenterBlock / 64) {
+        const int row = j0 + r;                         // (wave-uniform)
+        double t = 0.0;
+        if (row < n) {
+            const double* src = X + (int64_t)row * n;
+            for (int i = lane; i < row; i += 64) t += src[i];
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+        if (lane == 0) row_part[r] = t;
+    }
+    __syncthreads();
+    if (wave == 0 && j < n) {
+        double v = 0.0;
+#pragma unroll
+        for (int w = 0; w < kCenterBlock / 64; ++w) v += col_part[w][lane];
+        s[j] = v + row_part[lane];
+    }
+}
+
+// inverse_center: X_ij -= (s_i + s_j) / n - mu for i >= j, 64 x 64 blocks.  Every block adds up s itself (n <= a few thousand doubles from the
+// L2; thread-strided sums, wave shuffles, the four wave sums in index order: the same bits in every block).  grid: (nb, nb), nb = ceil(n / 64);
+// blocks above the diagonal return.
+__global__ __launch_bounds__(kCenterBlock) void inverse_center(double* __restrict__ X, int n, const double* __restrict__ s) {
+    const int bi = blockIdx.y, bj = blockIdx.x;
+    if (bj > bi) return;
+    __shared__ double red[kCenterBlock / 64];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double t = 0.0;
+    for (int i = threadIdx.x; i < n; i += kCenterBlock) t += s[i];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) t += __shfl_down(t, off, 64);
+    if (lane == 0) red[wave] = t;
+    __syncthreads();
+    double total = 0.0;
+#pragma unroll
+    for (int w = 0; w < kCenterBlock / 64; ++w) total += red[w];
+    const double inv_n = 1.0 / (double)n, mu = total * inv_n * inv_n;
+    const int col = bj * 64 + lane;
+    if (col >= n) return;
+    const double sj = s[col];
+    for (int r = wave; r < 64; r += kCenterBlock / 64) {
+        const int row = bi * 64 + r;
+        if (row < n && row >= col) X[(int64_t)row * n + col] -= (s[row] + sj) * inv_n - mu;
+    }
+}
+
 // ---- colouring of level 0 on the device (gmg_config::device_coloring) ----------------------------------------------------------------
 // Jones-Plassmann in synchronous rounds, first fit: host_plan.hpp::jp_coloring_host is the specification, the bytes are the same bit for bit
 // (tests/test_gpu_device_coloring.py).  One launch of jp_round is one round; stream order separates the rounds, nothing waits for another

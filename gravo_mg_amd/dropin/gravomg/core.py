@@ -311,7 +311,10 @@ class MultigridSolver(object):
         reorder_pointwise (0 = default; 1: with smoother 1 or 2 the finest level is renumbered for locality as it is for the multicolour smoother -- inputs in
         arbitrary vertex order, point clouds; gmg_config::reorder_pointwise),
         zero_guess_step (0 = default; 1: with smoother 1 or 2 a first step on a zero guess is c * b / diag, no zero vector is written or read; the same
-        iterates, gmg_config::zero_guess_step)."""
+        iterates, gmg_config::zero_guess_step),
+        nullspace (0 = default: symmetric positive definite systems; 1: symmetric positive semi-definite systems with the constants as their null space -- the
+        stiffness matrix or the Bilaplacian of a connected mesh as it is, no mass term: the coarsest solve applies the pseudo-inverse, the right-hand side is
+        projected onto the range and the solution comes back with zero mass-weighted mean; one device only, gmg_config::nullspace)."""
         self.solver.set_engine_option(str(key), float(value))
         if str(key) == "device":
             self._device = int(value)

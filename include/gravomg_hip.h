@@ -153,6 +153,30 @@ typedef struct {
     int color_ahead;       /* 1 (default): a gmg_set_system that cannot be a values-only refresh starts the greedy colouring of level 0 (one core, 10-13 ms at
                               3 M vertices: the longest task of a cold set-up) at entry, beside the inspection of the caller's arrays, with every index checked;
                               the result is used when the inspection and the layout decisions allow it -- the same colours, ~6 ms earlier.  0: after them */
+    int nullspace;         /* 0 (default): the handle's systems are symmetric positive definite.  1: they are symmetric positive SEMI-definite with the null space
+                              span{1} -- stiffness matrices and Bilaplacians of a connected mesh or point graph, handed over as they are (no mass term) -- on a
+                              hierarchy whose prolongations preserve constants (rows of every U_k sum to 1: every built-in weighting).  DESIGN.md 5f.
+                              Every gmg_set_system, values-only refresh and gmg_set_system_values_device checks the claim: max_i |sum_j a_ij| / sum_j |a_ij|
+                              of level 0 (one device kernel, gmgs::rowsum_rows) and of the coarsest Galerkin operator (host) must not exceed 1e-9 -- level 0
+                              above it: GMG_ERR_INVALID ("nullspace = 1 but A 1 != 0"), the coarsest above it: GMG_ERR_NUMERIC ("the prolongations do not
+                              preserve constants"); a zero pivot before the last one (a disconnected graph) stays GMG_ERR_NUMERIC; a failed call leaves the
+                              handle without a system.  The coarsest solve applies the pseudo-inverse A_L^+: the last pivot of the LDL^T (rounding noise) is
+                              accepted whatever it is and replaced so that 1 / D = 0 -- the factor then solves with G = [[A11^-1, 0], [0, 0]] -- and
+                              P G P = A_L^+ with P = I - 1 1^T / n_L: the device modes double-centre the inverse they build (gmgs::inverse_col_sums,
+                              gmgs::inverse_center, before the mirror / pack kernels; the fp32 twin and the packed triangle inherit it), GMG_COARSE_HOST_LDLT
+                              removes the mean of the right-hand side before and of the answer after the back-substitution; gmg_coarse_solve applies A_L^+.
+                              gmg_solve, gmg_solve_x0_rhs and gmg_solve_device project at their two ends (nullspace_kernels.hip.hpp): after the load
+                              b <- b - (1^T b / n) 1, the orthogonal projection onto range(A) -- the residual checks see the projected b --, and before the
+                              fetch or scatter x <- x - (m^T x / m^T 1) 1 with m the handle's mass (unit weights when none was set): the caller gets the
+                              solution of zero mass-weighted mean, the reported residue is unchanged because A 1 = 0.  Works with every smoother,
+                              accelerate, pcg, inner_precision, use_graph and all four coarse modes.  Unchanged by this field, nothing projected:
+                              gmg_load_problem / gmg_run_cycles / gmg_vcycle / gmg_profile_cycle and the operator entry points.  One device only: on such
+                              a handle gmg_p2p_prepare, and gmg_dist_setup / gmg_dist_partition with world > 1, return GMG_ERR_UNSUPPORTED.  Timing keys,
+                              written by such handles only: "nullspace" (1), "nullspace_rowsum_l0", "nullspace_rowsum_coarse", "nullspace_pinned_pivot" (the
+                              replaced pivot over the largest pivot) at set-up, "nullspace_rhs_defect" (max over the columns of |1^T b| / (sqrt(n) |b|_2) before
+                              the projection) at every solve.  Values other than 0 / 1: GMG_ERR_INVALID (gmg_last_error(NULL) names the field), decided
+                              before a device is looked for.  In front of fold_head, like fold_head in front of accelerate: a binding built against another
+                              edition is refused by gmg_config_size */
     int fold_head;         /* 1 (default): where speculate_head enqueues a head, the residual check in front of it also computes the first colour update of the
                               next cycle -- it has read those rows and holds every operand -- and stores it to a side vector; the launch enqueued ahead of
                               the decision is then the SECOND colour launch, which takes the first colour's values from the side vector and copies them into
@@ -313,7 +337,7 @@ int gmg_spmv(gmg_handle h, int k, const double* x, int d, double* y);
 int gmg_restrict(gmg_handle h, int k, const double* r, int d, double* rc);
 /* x += U_k e : multigrid_solver.cpp:1082. */
 int gmg_prolong_add(gmg_handle h, int k, const double* e, int d, double* x);
-/* e = A_L^{-1} rc with the configured coarse solver: multigrid_solver.cpp:1075. */
+/* e = A_L^{-1} rc with the configured coarse solver: multigrid_solver.cpp:1075 (gmg_config::nullspace = 1: e = A_L^+ rc). */
 int gmg_coarse_solve(gmg_handle h, const double* rc, int d, double* e);
 /* residualCheck(A_0, b, x, type), multigrid_solver.cpp:1228-1277 (types 0..3). */
 int gmg_residual_norm(gmg_handle h, const double* b, const double* x, int d, int type, double* out);

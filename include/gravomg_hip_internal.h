@@ -167,6 +167,18 @@ int gmg_p2p_debug_collective_roundtrip(gmg_handle h, double* max_abs_diff, long 
  * factor with the simplicial one.  The report (text lines) goes to `report` (cap bytes, NUL-terminated). */
 int gmg_host_ldlt_probe(int n, const int* colptr, const int* rowidx, const double* val, const double* b, int reps, char* report, int cap);
 
+/* Host-only views of gmg_config::nullspace = 1, for CPU tests.
+ * gmg_host_nullspace_rowsum: the set-up's rule on a caller's matrix -- *rowsum = max_i |sum_j a_ij| / sum_j |a_ij| (an empty or all-zero row
+ * counts 0); above 1e-9 the return value is the one gmg_set_system gives: GMG_ERR_INVALID with coarsest = 0 (level 0: "A 1 != 0"),
+ * GMG_ERR_NUMERIC with coarsest != 0 ("the prolongations do not preserve constants").
+ * gmg_host_pinv_solve: x = P G P b with the coarsest solver's factor in its "pin the last pivot" mode (csrc/host_ldlt.hpp: the last pivot in
+ * elimination order accepted whatever it is, 1 / D = 0 in its place; G = [[A11^-1, 0], [0, 0]]) and P = I - 1 1^T / n, the means removed as
+ * GMG_COARSE_HOST_LDLT removes them -- A^+ b for a symmetric positive semi-definite A with null space span{1}.  b / x column-major n x d.
+ * The row-sum rule is applied first (GMG_ERR_NUMERIC above the bound); GMG_ERR_NUMERIC also for a zero pivot before the last one (a graph of
+ * two components).  info (optional, 2 doubles): the row-sum figure, the replaced pivot over the largest pivot. */
+int gmg_host_nullspace_rowsum(int n, const int* colptr, const int* rowidx, const double* val, int coarsest, double* rowsum);
+int gmg_host_pinv_solve(int n, const int* colptr, const int* rowidx, const double* val, const double* b, int d, double* x, double* info);
+
 #ifdef __cplusplus
 }
 #endif
