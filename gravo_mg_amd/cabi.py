@@ -44,7 +44,7 @@ class GmgConfig(C.Structure):
         ("row_align", C.c_int), ("block_rows", C.c_int), ("block_lanes", C.c_int), ("block_from_level", C.c_int),
         ("device_setup", C.c_int), ("device_rap", C.c_int), ("reorder_fine", C.c_int), ("inner_precision", C.c_int), ("block_csr", C.c_int), ("host_threads", C.c_int),
         ("verbose", C.c_int), ("gs_omega", C.c_double), ("restrict_sigma", C.c_int), ("block_ep", C.c_int), ("dist_shard_levels", C.c_int), ("block_fine", C.c_int), ("fine_col16", C.c_int), ("stream_gate", C.c_int), ("dist_exchange", C.c_int), ("prepare_structure", C.c_int), ("fuse_restrict_sweep", C.c_int), ("speculate_head", C.c_int), ("uniform_slices", C.c_int), ("color_ahead", C.c_int),
-        ("nullspace", C.c_int), ("fold_head", C.c_int), ("reorder_pointwise", C.c_int), ("zero_guess_step", C.c_int), ("pcg", C.c_int), ("device_coloring", C.c_int), ("accelerate", C.c_int),
+        ("precond_precision", C.c_int), ("nullspace", C.c_int), ("fold_head", C.c_int), ("reorder_pointwise", C.c_int), ("zero_guess_step", C.c_int), ("pcg", C.c_int), ("device_coloring", C.c_int), ("accelerate", C.c_int),
     ]
 
 
@@ -356,7 +356,7 @@ class Engine:
 
     def __init__(self, smoother=SMOOTHER_MULTICOLOR_GS, pre_iters=2, post_iters=2, jacobi_omega=0.67,
                  coarse_mode=COARSE_AUTO, use_graph=False, sigma=0, row_align=64, block_rows=64, block_from_level=1, block_lanes=0,
-                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None, device_coloring=None, pcg=0, reorder_pointwise=None, zero_guess_step=None, nullspace=0):
+                 device_setup=True, device_rap=True, reorder_fine=2, inner_precision=0, block_csr=True, device=0, verbose=False, gs_omega=None, block_ep=None, restrict_sigma=None, dist_shard_levels=None, block_fine=None, fine_col16=None, stream_gate=None, prepare_structure=None, dist_exchange=None, fuse_restrict_sweep=None, speculate_head=None, uniform_slices=None, color_ahead=None, accelerate=0, fold_head=None, device_coloring=None, pcg=0, reorder_pointwise=None, zero_guess_step=None, nullspace=0, precond_precision=0):
         l = lib()
         cfg = GmgConfig()
         l.gmg_config_default(C.byref(cfg))
@@ -403,6 +403,7 @@ class Engine:
             cfg.zero_guess_step = int(zero_guess_step)       # 0 / 1: a pointwise smoother's first step on a zero guess is c * b / diag (gmg_config::zero_guess_step)
         cfg.nullspace = int(nullspace)            # 0: positive definite systems; 1: semi-definite with the null space span{1} (gmg_config::nullspace)
         cfg.pcg = int(pcg)                        # 0: the plain loop; 1: CG preconditioned by the (symmetric) V-cycle (gmg_config::pcg)
+        cfg.precond_precision = int(precond_precision)   # 0: that cycle in fp64; 1: the fp32 cycle on the fp32 twins (gmg_config::precond_precision)
         self._h = _vp()
         rc = l.gmg_create(C.byref(cfg), C.byref(self._h))
         if rc:

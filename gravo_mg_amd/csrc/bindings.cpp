@@ -343,6 +343,7 @@ public:
         else if (key == "reorder_pointwise") c.reorder_pointwise = (int)value;
         else if (key == "zero_guess_step") c.zero_guess_step = (int)value;
         else if (key == "nullspace") c.nullspace = (int)value;
+        else if (key == "precond_precision") c.precond_precision = (int)value;
         else throw std::invalid_argument("unknown engine option: " + key);
     }
 

@@ -139,6 +139,7 @@ int gmg_config_default(gmg_config* cfg) try {
     cfg->prepare_structure = 1;
     cfg->fuse_restrict_sweep = 1;
     cfg->speculate_head = 1;
+    cfg->precond_precision = 0; // a pcg = 1 handle applies its cycle in fp64 (1: the fp32 cycle on the fp32 twins, see gmg_config)
     cfg->nullspace = 0;       // symmetric positive definite systems (1: semi-definite with the null space span{1}, see gmg_config)
     cfg->fold_head = 1;
     cfg->uniform_slices = 1;
@@ -191,6 +192,8 @@ int gmg_create(const gmg_config* cfg, gmg_handle* out) try {
         if (c.accelerate != 0) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg and gmg_config::accelerate are two solve loops: set one of them");
         if (c.inner_precision != 0) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::pcg is fp64 only (inner_precision = 0)");
     }
+    if (c.precond_precision < 0 || c.precond_precision > 1) return create_refused(GMG_ERR_INVALID, "gmg_config::precond_precision must be 0 or 1");
+    if (c.precond_precision && !c.pcg) return create_refused(GMG_ERR_UNSUPPORTED, "gmg_config::precond_precision = 1 needs gmg_config::pcg = 1: it is the precision of that loop's preconditioner cycle");
     gmg_handle h = new gmg_solver_s();
     h->cfg = c;
     h->coarse.pin_last = c.nullspace != 0;      // the coarsest factor takes its last pivot for what it is (host_ldlt.hpp)
@@ -896,20 +899,27 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
     // gmg_config::pcg = 1: conjugate gradients with the cycle as the preconditioner (launch_pcg_step).  The cycle runs on the CG
     // residual from a zero guess, so for the duration of the loop level 0's x / b are z / r and the CG iterate and the true right-hand side live in
     // the PCG state (pcg_exchange); the confirming check -- as in the accelerated branch -- and the caller's fetch() see them exchanged back.
+    // gmg_config::precond_precision = 1: z = (double) cycle32(fl32(r)).  The fp32 cycle reads level 0's b32 and leaves z in x32; it does not touch
+    // level 0's fp64 x / b, so the CG iterate and the true right-hand side stay where they are -- nothing is exchanged -- and r lives in the PCG
+    // state (pcg.b).  (Level 0 is never the coarsest level, whose fp32 solve converts through its fp64 vectors: gmg_set_system refuses a hierarchy
+    // without a transfer level.)  fl32(r) reaches b32 from pcg_update; the fresh residuals (the first, and after a confirmation that did not hold) through launch_cvt.
     const int pcg = h->cfg.pcg;
+    const bool pcg32 = pcg && h->cfg.precond_precision;
+    const size_t l0_count = (size_t)l0.n_pad * d;
     int pcg_confirmations = 0;
     bool pcg_first = true, pcg_fresh = false;
     struct PcgRestore { gmg_handle h; ~PcgRestore() { if (h->pcg.exchanged) pcg_exchange(h); } } pcg_restore{h};        // (every way out, errors included)
     auto pcg_step = [&](SolveRule& rule, double& residue, int&) -> int {
         // z = cycle(rhs = r, x = 0); with gmg_config::zero_guess_step the cycle knows that its guess is zero and nobody writes the zeros
-        if ((rc = vcycle_legs<double>(h, d, -1, kPcgGraphSalt, 0, nullptr, /*zero_guess*/ true))) return rc;
+        if ((rc = pcg32 ? vcycle_legs<float>(h, d, -1, kPcgGraphSalt32, 0, nullptr, /*zero_guess*/ true, /*precond*/ true)
+                        : vcycle_legs<double>(h, d, -1, kPcgGraphSalt, 0, nullptr, /*zero_guess*/ true))) return rc;
         if ((rc = launch_pcg_step(h, d, stop_type, pcg_first, pcg_fresh))) return rc;
         pcg_first = pcg_fresh = false;
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
         if (rule_goes_on(rule_after(rule, residue))) return GMG_OK;
         const double recurrence = residue;
-        pcg_exchange(h);                                                          // level 0 holds the iterate and the true right-hand side
+        if (!pcg32) pcg_exchange(h);                                              // level 0 holds the iterate and the true right-hand side
         if ((rc = launch_norm(h, d, stop_type))) return rc;                       // it would end the loop: the check on the iterate itself decides
         if ((rc = wait_norm(h))) return rc;
         residue = norm_from_sums(h->h_norm, d, stop_type);
@@ -918,7 +928,8 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         // (confirmed, above the tolerance and the loop will go on: r is recomputed from the iterate, the next step starts a new recurrence)
         if (rule_goes_on(rule_after(rule, residue))) {
             launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->pcg.b);
-            pcg_exchange(h);
+            if (pcg32) launch_cvt(h, h->pcg.b.get(), l0.b32.get(), l0_count);
+            else pcg_exchange(h);
             pcg_fresh = true;
         }
         return GMG_OK;
@@ -956,14 +967,20 @@ static int solve_common(gmg_handle h, const char* bad_args, int d, double tol, i
         HIPCHK(hipMemsetAsync(h->pcg.scal, 0, sizeof(double) * ((size_t)4 * h->pcg.d + 2), h->stream));
         launch_spmv<double>(h, l0, d, 1, l0.b, l0.x, h->pcg.b);                  // r = b - A x0
         // the first cycle's zero guess (later ones: pcg_direction) -- unless the cycle starts from zero by itself (level0_zero_guess)
-        if (!level0_zero_guess(h)) HIPCHK(hipMemsetAsync(h->pcg.x, 0, sizeof(double) * (size_t)l0.n_pad * d, h->stream));
-        pcg_exchange(h);
+        if (pcg32) {
+            launch_cvt(h, h->pcg.b.get(), l0.b32.get(), l0_count);               // fl32(r): the first cycle's right-hand side (later ones: pcg_update)
+            if (!level0_zero_guess(h)) HIPCHK(hipMemsetAsync(l0.x32, 0, sizeof(float) * l0_count, h->stream));
+        } else {
+            if (!level0_zero_guess(h)) HIPCHK(hipMemsetAsync(h->pcg.x, 0, sizeof(double) * l0_count, h->stream));
+            pcg_exchange(h);
+        }
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, pcg_step);
     } else
         verdict = solve_loop(h, tol, max_iter, t0, conv, h->cfg.verbose, iters_out, residue_out, plain_step);
     if (verdict < 0) return verdict;
     if (h->pcg.exchanged) return fail(h, GMG_ERR_STATE, "the preconditioned CG loop ended without its confirming check");      // (cannot happen: solve_loop ends where the step confirmed)
     h->timing["pcg"] = pcg;
+    if (pcg32) h->timing["precond_precision"] = 1;
     h->timing["pcg_confirmations"] = pcg_confirmations;
     double pcg_counts[2] = {0.0, 0.0};
     if (pcg) {

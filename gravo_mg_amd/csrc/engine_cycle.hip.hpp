@@ -654,7 +654,7 @@ int ensure_vectors(gmg_handle h, int d) {
         return rc;
     };
     for (auto& l : h->lv) {
-        const bool tmp = pointwise_smoother(h->cfg) || l.ord.blocked, f32 = h->cfg.inner_precision != 0;
+        const bool tmp = pointwise_smoother(h->cfg) || l.ord.blocked, f32 = fp32_cycle_wanted(h->cfg);
         int rc;
         if ((rc = vec(l.x, l, true)) || (rc = vec(l.b, l, true)) || (rc = vec(l.r, l, true)) || (rc = vec(l.tmp, l, tmp)) ||
             (rc = vec(l.x32, l, f32)) || (rc = vec(l.b32, l, f32)) || (rc = vec(l.r32, l, f32)) || (rc = vec(l.tmp32, l, f32 && tmp))) return rc;
@@ -1175,9 +1175,12 @@ int run_graph(gmg_handle h, int key, F&& enqueue) {
 // graph); decide: the check's reduction also takes the loop's decision (CycleWatch; not the mixed-precision check: no head is eligible there).
 // zero_guess: the caller's x of level 0 is the zero vector by construction and holds anything (the preconditioner application of the CG loop); the
 // fp32 inner cycle always starts so.  Where the smoother can start without a materialised zero (level0_zero_guess) nothing zeroes or reads it.
+// precond (T = float; the CG loop of gmg_config::precond_precision = 1): head, down, coarse and up only -- the caller has put the right-hand side
+// into level 0's b32 and zeros into x32 (unless level0_zero_guess), takes the result from x32 and wants neither the correction added to the fp64
+// iterate nor a new defect: level 0's fp64 x and b are not touched.  Such graphs need a key_salt of their own.
 inline bool level0_zero_guess(gmg_handle h) { return pointwise_smoother(h->cfg) && h->L >= 1 && smooth_from_zero_ok(h, h->lv[0], h->cfg.pre_iters); }
 template <class T>
-int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done, const CycleWatch* decide, bool zero_guess = false) {
+int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done, const CycleWatch* decide, bool zero_guess = false, bool precond = false) {
     int rc;
     const int nt = norm_type < 0 ? 9 : norm_type;
     constexpr bool mixed = sizeof(T) == 4;
@@ -1187,10 +1190,11 @@ int vcycle_legs(gmg_handle h, int d, int norm_type, int key_salt, int head_done,
     // mixed precision: the fp32 cycle starts from a zero guess on the defect b32 = b - A x (already in place), its
     // result is added to the fp64 iterate, and the new defect + its norms are formed in one fp64 pass
     const bool x0_zero = (mixed || zero_guess) && level0_zero_guess(h);
-    auto head = [&] { if (mixed && !x0_zero) (void)hipMemsetAsync(h->lv[0].x32, 0, sizeof(float) * (size_t)h->lv[0].n_pad * d, h->stream); };
+    auto head = [&] { if (mixed && !precond && !x0_zero) (void)hipMemsetAsync(h->lv[0].x32, 0, sizeof(float) * (size_t)h->lv[0].n_pad * d, h->stream); };
     // (folded: what the way up returned -- both in one enqueue body, which under a graph runs at capture only)
     auto tail = [&](int& err, int folded) {
-        if (mixed) {
+        if (mixed && precond) {
+        } else if (mixed) {
             const size_t cnt = (size_t)h->lv[0].n_pad * d;
             hipLaunchKernelGGL(gmgk::add_correction, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, h->stream, h->lv[0].x32, h->lv[0].x, (int64_t)cnt);
             err = launch_residual_to_f32(h, d, norm_type);
@@ -1285,16 +1289,20 @@ int launch_accel_step(gmg_handle h, int d, int type, int done) {
 // Graphs of the cycle captured while the owners are exchanged hold the exchanged buffers: a key of their own (vcycle_legs' key_salt).  The two
 // states hand lv[0].x / lv[0].b the same two pairs of buffers for as long as the level vectors live (every solve exchanges an even number of times).
 constexpr int kPcgGraphSalt = 200000;
+// ... and the fp32 cycle without head and tail (gmg_config::precond_precision = 1) is another graph than the inner cycle's (salt 100000)
+constexpr int kPcgGraphSalt32 = 300000;
 
-// its vectors and scalars, for the level vectors as they are now (n_pad x dcap)
+// its vectors and scalars, for the level vectors as they are now (n_pad x dcap).  gmg_config::precond_precision = 1 exchanges nothing: b (there: r)
+// and p only
 int ensure_pcg(gmg_handle h) {
     auto& a = h->pcg;
     const int n_pad = h->lv[0].n_pad, D = h->dcap;
-    if (a.x && a.d == D && a.n_pad == n_pad) return GMG_OK;
+    if (a.p && a.d == D && a.n_pad == n_pad) return GMG_OK;
     a = {};
     const size_t count = (size_t)n_pad * D;
     int rc;
     for (DevBuf<double>* p : {&a.x, &a.b, &a.p}) {
+        if (p == &a.x && h->cfg.precond_precision) continue;
         if ((rc = dev_alloc(h, *p, count))) return rc;
         HIPCHK(hipMemsetAsync(*p, 0, sizeof(double) * count, h->stream));          // (padding rows: zero, and no kernel writes anything else there)
     }
@@ -1311,11 +1319,15 @@ void pcg_exchange(gmg_handle h) {
     h->pcg.exchanged = !h->pcg.exchanged;
 }
 
-// One CG step behind the cycle, owners exchanged: lv[0].b holds r, lv[0].x holds z = cycle(r, 0), pcg.x the iterate, pcg.b the true b.
-// first: the first iteration of the solve; fresh: r was recomputed from the iterate.  Leaves the new iterate in pcg.x, the recurrence residual
-// in lv[0].b, zeros in lv[0].x (z itself where the next cycle starts from zero without them: level0_zero_guess) and the check's sums on their way
-// to h_norm (wait_norm).
-int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
+// One CG step behind the cycle.  first: the first iteration of the solve; fresh: r was recomputed from the iterate.  Who holds what:
+//   fp64 cycle, owners exchanged: lv[0].b holds r, lv[0].x holds z = cycle(r, 0), pcg.x the iterate, pcg.b the true b;
+//   gmg_config::precond_precision = 1, nothing exchanged: lv[0].x the iterate, lv[0].b the true b, pcg.b holds r, z is lv[0].x32 (float), and
+//   pcg_update leaves fl32(r) in lv[0].b32, the next cycle's right-hand side.
+// Leaves the new iterate and the recurrence residual there, zeros in z (z itself where the next cycle starts from zero without them:
+// level0_zero_guess) and the check's sums on their way to h_norm (wait_norm).  The same launches in the same order for both.
+template <class TZ>
+int launch_pcg_step_on(gmg_handle h, int d, int type, bool first, bool fresh, double* x, double* r, TZ* z, const double* b, float* r32) {
+    constexpr bool mixed = sizeof(TZ) == 4;
     auto& a = h->pcg;
     Level& l = h->lv[0];
     const int DA = a.d, ld = l.n_pad, n_pairs = l.n_pad / 2;
@@ -1324,14 +1336,14 @@ int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
     double *rho = a.scal, *beta = a.scal + DA, *alpha = a.scal + 2 * DA, *restart = a.scal + 3 * DA, *guard_steps = a.scal + 4 * DA, *restarts = a.scal + 4 * DA + 1;
     // the check's sums of the last update or confirmation, where the device reads them (launch_reduce)
     const double* sums = first ? nullptr : (polled(h) ? h->h_norm : h->d_norm.get());
-    double *r = l.b, *z = l.x, *q = l.r;
+    double* q = l.r;
     for_col_chunks(d, [&](int c0, int dc) {
         const size_t off = (size_t)c0 * ld;
-        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, r + off, z + off, ld, n_pairs, a.partials));
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D, TZ>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, r + off, z + off, ld, n_pairs, a.partials));
         hipLaunchKernelGGL(gmgk::pcg_reduce_beta, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, rho + c0, beta + c0, restart + c0,
                            (int)first, (int)fresh, restarts);
         // (the next cycle's zero guess: written here unless that cycle starts from zero by itself)
-        DISPATCH_D(dc, DISPATCH_FLAG(ZERO_Z, !level0_zero_guess(h), hipLaunchKernelGGL((gmgk::pcg_direction<D, ZERO_Z>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream,
+        DISPATCH_D(dc, DISPATCH_FLAG(ZERO_Z, !level0_zero_guess(h), hipLaunchKernelGGL((gmgk::pcg_direction<D, ZERO_Z, TZ>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream,
                                           z + off, a.p + off, beta + c0, ld, n_pairs)));
     });
     launch_spmv<double>(h, l, d, 0, nullptr, a.p.get(), q);
@@ -1340,12 +1352,19 @@ int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
         DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_dot<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.p + off, q + off, ld, n_pairs, a.partials));
         hipLaunchKernelGGL(gmgk::pcg_reduce_alpha, dim3(1), dim3(gmgk::kReduceBlock), 0, h->stream, a.partials, nblk, dc, rho + c0, alpha + c0, restart + c0,
                            sums ? sums + 2 * c0 : nullptr, guard_steps);
-        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_update<D>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, a.x + off, r + off, a.p + off, q + off, alpha + c0,
-                                          a.b + off, w, ld, n_pairs, a.partials));
+        DISPATCH_D(dc, hipLaunchKernelGGL((gmgk::pcg_update<D, mixed>), dim3(nblk), dim3(gmgk::kAccelBlock), 0, h->stream, x + off, r + off, a.p + off, q + off, alpha + c0,
+                                          b + off, w, ld, n_pairs, a.partials, mixed ? r32 + off : nullptr));
         launch_reduce(h, nblk, dc, c0, c0 + 4 >= d, a.partials);
     });
     if (!polled(h)) HIPCHK(hipMemcpyAsync(h->h_norm, h->d_norm, sizeof(double) * 2 * d, hipMemcpyDeviceToHost, h->stream));
     return GMG_OK;
+}
+
+int launch_pcg_step(gmg_handle h, int d, int type, bool first, bool fresh) {
+    auto& a = h->pcg;
+    Level& l = h->lv[0];
+    if (h->cfg.precond_precision) return launch_pcg_step_on<float>(h, d, type, first, fresh, l.x, a.b, l.x32.get(), l.b, l.b32);
+    return launch_pcg_step_on<double>(h, d, type, first, fresh, a.x, l.b, l.x.get(), a.b, nullptr);
 }
 
 // ---- the projections of a solve on a semi-definite system (gmg_config::nullspace; engine.hip::solve_common; kernels: nullspace_kernels.hip.hpp) ----

@@ -263,6 +263,8 @@ struct gmg_solver_s {
     // lv[0].x the preconditioned residual z, so x and b below own the CG iterate and the true right-hand side; the owners are exchanged
     // (pcg_exchange, `exchanged` says which way round they are) for the confirming check and before the solve returns: outside solve_common
     // lv[0].x / lv[0].b are what they are on every handle, and x / b here two spare buffers.  q = A p lives in lv[0].r.
+    // gmg_config::precond_precision = 1: the fp32 cycle works on lv[0].b32 / x32 and leaves lv[0].x / b alone, so nothing is exchanged (`exchanged`
+    // stays false): lv[0].x is the CG iterate and lv[0].b the true right-hand side throughout, b here holds r, and x is not allocated.
     struct PcgState {
         DevBuf<double> x, b, p;
         DevBuf<double> scal;             // rho[d], beta[d], alpha[d], restart[d] (1: the column took a guard, its next iteration is fresh), guarded steps, restarts: 4 d + 2 doubles
@@ -615,6 +617,9 @@ constexpr int kEpMaxBlockLower = 3584;          // ... and largest lower chunk (
 constexpr int kBcsrMaxBlockEntries = 4096;      // largest block the block-CSR sweep stages in LDS (48 KB of fp64 entries)
 // Smoothers whose step is one pass x_out = f(x_in) over all rows (weighted Jacobi, Chebyshev) and not a Gauss-Seidel sweep: no colour or block
 // order, ping-pong between x and tmp, no sweep-derived residual, no fused first sweep, no interleaved sweep output, a materialised zero guess.
+// the handle runs an fp32 cycle somewhere -- the inner cycle of inner_precision = 1 or the CG loop's preconditioner of precond_precision = 1 --
+// and so keeps fp32 twins of its operators (refresh_fp32_twins) and fp32 level vectors (ensure_vectors)
+inline bool fp32_cycle_wanted(const gmg_config& c) { return c.inner_precision != 0 || c.precond_precision != 0; }
 inline bool pointwise_smoother(const gmg_config& c) { return c.smoother == GMG_SMOOTHER_JACOBI || c.smoother == GMG_SMOOTHER_CHEBYSHEV; }
 inline const char* smoother_name(const gmg_config& c) {
     return c.smoother == GMG_SMOOTHER_JACOBI ? "GMG_SMOOTHER_JACOBI" : (c.smoother == GMG_SMOOTHER_CHEBYSHEV ? "GMG_SMOOTHER_CHEBYSHEV" : "GMG_SMOOTHER_MULTICOLOR_GS");

@@ -346,7 +346,7 @@ int finish_system(gmg_handle h, int n, double ms_factor, bool inverse_ready, boo
     if (!h->coarse_device) h->timing["coarse_inverse_bytes"] = 0.0;
     if (h->coarse_device && !inverse_ready && (rc = build_coarse_inverse_device(h))) return rc;
     if (h->cfg.smoother == GMG_SMOOTHER_CHEBYSHEV && !placeholder && (rc = compute_cheby_bounds(h))) return rc;      // (the real values bring the bounds: no keys before a gmg_set_system)
-    if (h->cfg.inner_precision && (rc = refresh_fp32_twins(h, alloc_twins))) return rc;
+    if (fp32_cycle_wanted(h->cfg) && (rc = refresh_fp32_twins(h, alloc_twins))) return rc;
     if (!placeholder && !h->mass.empty() && (h->mass_dirty || !h->d_mass)) {
         if ((int)h->mass.size() != n) return fail(h, GMG_ERR_INVALID, "mass size does not match the system");
         if ((rc = upload_mass(h))) return rc;

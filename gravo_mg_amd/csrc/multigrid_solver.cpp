@@ -243,13 +243,13 @@ uint64_t MultigridSolver::configKey() const {
 int MultigridSolver::ensureEngine() {
     gmg_config want = engineConfig;
     want.pre_iters = preIters; want.post_iters = postIters; want.verbose = 0;
-    if (exactGsActive_) { want.smoother = GMG_SMOOTHER_MULTICOLOR_GS; want.block_rows = 0; want.gs_omega = 1.0; want.pcg = 0; }      // scoped fallback, see solve() (a Gauss-Seidel cycle is no preconditioner for CG)
+    if (exactGsActive_) { want.smoother = GMG_SMOOTHER_MULTICOLOR_GS; want.block_rows = 0; want.gs_omega = 1.0; want.pcg = 0; want.precond_precision = 0; }      // scoped fallback, see solve() (a Gauss-Seidel cycle is no preconditioner for CG; precond_precision goes with pcg)
     if (engine_ && !configEqual(want, createdWith_)) {
         // An engine is PARKED only across the switch configured <-> exact-GS fallback (an application alternating between systems switches
         // engines, it does not rebuild them).  Any other change of configuration destroys the old engines: a parked one keeps its whole
         // device state -- hierarchy, level operators, vectors: several GB at 3 M vertices.
         auto fallbackPair = [](gmg_config a, gmg_config b) {
-            a.smoother = b.smoother = GMG_SMOOTHER_MULTICOLOR_GS; a.block_rows = b.block_rows = 0; a.gs_omega = b.gs_omega = 1.0; a.pcg = b.pcg = 0;
+            a.smoother = b.smoother = GMG_SMOOTHER_MULTICOLOR_GS; a.block_rows = b.block_rows = 0; a.gs_omega = b.gs_omega = 1.0; a.pcg = b.pcg = 0; a.precond_precision = b.precond_precision = 0;
             return configEqual(a, b);
         };
         if (parked_.engine && !configEqual(want, parked_.createdWith)) { gmg_destroy(parked_.engine); parked_ = ParkedEngine(); }

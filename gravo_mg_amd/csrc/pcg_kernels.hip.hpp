@@ -8,6 +8,9 @@
 //   pcg_pq          partial sums of <p, q>                                    -> pcg_reduce_alpha: alpha = rho / <p, q> or the guard (alpha = 0)
 //   pcg_update      x += alpha p,  r -= alpha q (alpha = 0: neither p nor q is read),  partial sums of w r^2, w b^2 (the residual check's)
 //
+// gmg_config::precond_precision = 1: z is the fp32 cycle's result (float) and pcg_update also writes fl32(r), that cycle's next right-hand side;
+// x, r, p, q, every sum and every scalar stay fp64 (the float instantiations below).
+//
 // <r, z> and <p, q> are plain Euclidean sums over the rows, PER COLUMN; the check's sums carry the stop type's weights.  Same form as
 // accel_kernels.hip.hpp, whose helpers are used: every kernel streams each vector once, two rows (16 bytes) per lane, on a fixed grid-stride map;
 // block partials are added by ONE block in index order (gmgk::reduce_partials for the check's sums): no floating-point atomics, the same input gives
@@ -19,9 +22,20 @@
 
 namespace gmgk {
 
-// partials[block][c] = this block's share of <u, v> in column c
-template <int DC>
-__global__ __launch_bounds__(kAccelBlock) void pcg_dot(const double* __restrict__ u, const double* __restrict__ v, int ld, int n_pairs,
+// gmg_config::precond_precision = 1: z comes out of the fp32 cycle (level 0's x32) and the cycle's right-hand side is fl32(r) (level 0's b32).
+// The kernels below then read z as float -- one 8-byte load beside the 16-byte ones, widened exactly -- on the SAME map and in the same
+// order of operations: a z that is exactly representable in fp32 gives the bits the all-fp64 instantiations give.
+__device__ __forceinline__ double2 pcg_ld2(const double* p, int64_t at) { return accel_ld2(p, at); }
+__device__ __forceinline__ double2 pcg_ld2(const float* p, int64_t at) {
+    const float2 v = *reinterpret_cast<const float2*>(p + at);
+    return make_double2((double)v.x, (double)v.y);
+}
+__device__ __forceinline__ void pcg_st2(double* p, int64_t at, double2 v) { accel_st2(p, at, v); }
+__device__ __forceinline__ void pcg_st2(float* p, int64_t at, double2 v) { *reinterpret_cast<float2*>(p + at) = make_float2((float)v.x, (float)v.y); }
+
+// partials[block][c] = this block's share of <u, v> in column c (TV = float: v is the fp32 cycle's z)
+template <int DC, class TV = double>
+__global__ __launch_bounds__(kAccelBlock) void pcg_dot(const double* __restrict__ u, const TV* __restrict__ v, int ld, int n_pairs,
                                                        double* __restrict__ partials) {
     double acc[DC];
 #pragma unroll
@@ -30,7 +44,7 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_dot(const double* __restrict_
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
             const int64_t at = 2 * (int64_t)i + (int64_t)c * ld;
-            const double2 uv = accel_ld2(u, at), vv = accel_ld2(v, at);
+            const double2 uv = accel_ld2(u, at), vv = pcg_ld2(v, at);
             acc[c] += uv.x * vv.x + uv.y * vv.y;
         }
     }
@@ -38,9 +52,10 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_dot(const double* __restrict_
 }
 
 // p = z + beta p (a column with beta = 0 writes p = z without reading p: what is there may be anything); ZERO_Z: z = 0 afterwards -- without it
-// z is only read (three vector passes instead of four): the next cycle starts from zero by itself (gmg_config::zero_guess_step)
-template <int DC, bool ZERO_Z = true>
-__global__ __launch_bounds__(kAccelBlock) void pcg_direction(double* __restrict__ z, double* __restrict__ p, const double* __restrict__ beta, int ld,
+// z is only read (three vector passes instead of four): the next cycle starts from zero by itself (gmg_config::zero_guess_step).
+// TZ = float: z is the fp32 cycle's (p = (double) z + beta p; ZERO_Z zeroes the fp32 vector, padding rows included: they stay zero)
+template <int DC, bool ZERO_Z = true, class TZ = double>
+__global__ __launch_bounds__(kAccelBlock) void pcg_direction(TZ* __restrict__ z, double* __restrict__ p, const double* __restrict__ beta, int ld,
                                                              int n_pairs) {
     double bt[DC];
 #pragma unroll
@@ -49,23 +64,31 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_direction(double* __restrict_
 #pragma unroll
         for (int c = 0; c < DC; ++c) {
             const int64_t at = 2 * (int64_t)i + (int64_t)c * ld;
-            double2 pn = accel_ld2(z, at);
+            double2 pn = pcg_ld2(z, at);
             if (bt[c] != 0.0) {
                 const double2 po = accel_ld2(p, at);
                 pn.x += bt[c] * po.x; pn.y += bt[c] * po.y;
             }
             accel_st2(p, at, pn);
-            if constexpr (ZERO_Z) accel_st2(z, at, make_double2(0.0, 0.0));
+            if constexpr (ZERO_Z) pcg_st2(z, at, make_double2(0.0, 0.0));
         }
     }
 }
 
 // x += alpha p, r -= alpha q; a column with alpha = 0 (the guard, pcg_scalars.hpp) keeps x and r and reads neither p nor q.
-// partials[block][2 c] = share of sum w r^2, [2 c + 1] = share of sum w b^2: the residual check's sums (gmgk::norm_term), for reduce_partials
-template <int DC>
+// partials[block][2 c] = share of sum w r^2, [2 c + 1] = share of sum w b^2: the residual check's sums (gmgk::norm_term), for reduce_partials.
+// R32 (gmg_config::precond_precision = 1): where r is written, fl32(r) -- the next fp32 cycle's right-hand side -- is written to r32 from the same
+// registers: no conversion pass over r.  A guarded column writes neither, so r32 must still hold what the previous iteration (or the fresh
+// residual's conversion) left there.  It does: no leg of the fp32 cycle writes level 0's right-hand side -- the smoother steps, the zero-guess
+// step and the residual product take it as a const operand (engine_cycle.hip.hpp: enqueue_down / enqueue_up reach level 0's b32 through
+// Prec<float>::b as the `b` of launch_smooth and launch_spmv only), a restriction writes the b32 of level k + 1 >= 1, and the coarsest solve's
+// conversions touch level L >= 1 (gmg_set_system refuses a hierarchy without a transfer level).
+// Padding rows: r is zero there and stays zero (p, q are), so r32 is written zero or not at all.
+template <int DC, bool R32 = false>
 __global__ __launch_bounds__(kAccelBlock) void pcg_update(double* __restrict__ x, double* __restrict__ r, const double* __restrict__ p,
                                                           const double* __restrict__ q, const double* __restrict__ alpha, const double* __restrict__ b,
-                                                          const double* __restrict__ w, int ld, int n_pairs, double* __restrict__ partials) {
+                                                          const double* __restrict__ w, int ld, int n_pairs, double* __restrict__ partials,
+                                                          float* __restrict__ r32 = nullptr) {
     double al[DC];
 #pragma unroll
     for (int c = 0; c < DC; ++c) al[c] = alpha[c];
@@ -84,6 +107,7 @@ __global__ __launch_bounds__(kAccelBlock) void pcg_update(double* __restrict__ x
                 accel_st2(x, at, make_double2(xv.x + al[c] * pv.x, xv.y + al[c] * pv.y));
                 rn = make_double2(rn.x - al[c] * qv.x, rn.y - al[c] * qv.y);
                 accel_st2(r, at, rn);
+                if constexpr (R32) pcg_st2(r32, at, rn);
             }
             acc[2 * c] += norm_term(rn.x, wv.x) + norm_term(rn.y, wv.y);
             acc[2 * c + 1] += norm_term(bv.x, wv.x) + norm_term(bv.y, wv.y);

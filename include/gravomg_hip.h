@@ -153,6 +153,25 @@ typedef struct {
     int color_ahead;       /* 1 (default): a gmg_set_system that cannot be a values-only refresh starts the greedy colouring of level 0 (one core, 10-13 ms at
                               3 M vertices: the longest task of a cold set-up) at entry, beside the inspection of the caller's arrays, with every index checked;
                               the result is used when the inspection and the layout decisions allow it -- the same colours, ~6 ms earlier.  0: after them */
+    int precond_precision; /* 0 (default): a pcg = 1 handle applies its preconditioner cycle in fp64 -- nothing changes, bit for bit.  1, with pcg = 1:
+                              gmg_solve, gmg_solve_x0_rhs and gmg_solve_device apply it as z = (double) cycle32(fl32(r)): the fp32 cycle on the fp32
+                              twins of every operator (those of inner_precision = 1) from a zero guess, its right-hand side the CG residual rounded to
+                              fp32.  CG only needs z ~ A^-1 r from a fixed symmetric positive definite operator; the iterate, the residual recurrence,
+                              q = A p, both inner products, the guards, the confirming residual check and the fresh recurrence after a confirmation that
+                              did not hold stay fp64 as gmg_config::pcg describes them, so the attainable accuracy is that of pcg = 1.  The streaming
+                              kernels read z as float and the update writes fl32(r) beside r (pcg_kernels.hip.hpp): no conversion passes.  The CG
+                              iterate and the true right-hand side stay in level 0's own vectors (nothing is exchanged); the mode allocates two fp64
+                              level-0 vectors (r, p) where pcg = 1 alone allocates three, plus the fp32 twins and fp32 level vectors of
+                              inner_precision = 1.  Works with both pointwise smoothers, use_graph, all four coarse modes,
+                              zero_guess_step, reorder_pointwise, nullspace = 1, d > 4, the values-only refresh and gmg_set_system_values_device
+                              (both refresh the twins).  Measured (profiles/pcg_precision): 0.64 - 0.85 of the time per iteration; it
+                              pays on the Bilaplacians, whose iteration count does not change (3 M, tau = 1e-9: 54.3 -> 34.6 ms to 1e-4), and does
+                              NOT pay on S + 1e-6 M systems, whose count more than doubles (3 M Poisson 6 -> 19 iterations, 4.0 -> 9.6 ms): fl32(r)
+                              perturbs their nearly-null constant.  Unchanged on such a handle, and fp64: gmg_vcycle, gmg_run_cycles, gmg_profile_cycle and the
+                              operator entry points.  1 without pcg = 1: GMG_ERR_UNSUPPORTED; values other than 0 / 1: GMG_ERR_INVALID; both decided
+                              before a device is looked for, gmg_last_error(NULL) names the field.  inner_precision = 1 stays refused with pcg = 1, and
+                              accelerate has no fp32 form.  Timing key, written by such handles only, at every solve: "precond_precision" (1).  In front
+                              of nullspace, like nullspace in front of fold_head: a binding built against another edition is refused by gmg_config_size */
     int nullspace;         /* 0 (default): the handle's systems are symmetric positive definite.  1: they are symmetric positive SEMI-definite with the null space
                               span{1} -- stiffness matrices and Bilaplacians of a connected mesh or point graph, handed over as they are (no mass term) -- on a
                               hierarchy whose prolongations preserve constants (rows of every U_k sum to 1: every built-in weighting).  DESIGN.md 5f.
